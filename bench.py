@@ -1,8 +1,18 @@
 """TP-GAN G+D train-step benchmark (BASELINE.json metric: faces/sec at 128x128, bs32/GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and no more: set up, W warm-up steps, K timed
+steps, the JSON line.  `--dump-outputs DIR` also writes, after the timed steps, what the timed path
+returns (the step's loss dict, one DIR/<name>.npy per entry, float32) in the second of two more
+steps run from the run's initial state -- seeded weights, zero Adam moments, the seeded batch.  The
+second step's losses come from weights that the first step's whole forward, backward and both Adam
+updates produced, so every timed kernel reaches them, and they depend on the arguments alone: two
+builds can be compared output for output.  `--full` adds
+everything else: the dominant-kernel probe (`roofline`, `roofline_kernels`) and the CPU baseline
+(`cpu_baseline`), described below.
 
 `--gpus N` (N > 1) without a launcher starts the second form itself, as a child process, and
 exits with its code; under a launcher every rank checks that --gpus equals WORLD_SIZE, and
@@ -14,7 +24,7 @@ with fp32 accumulate and fp32 master weights, synthetic Multi-PIE-shaped data re
 HBM, random-init weights.  Data parallel over N GPUs (one process per GPU, RCCL
 all-reduce of G and D gradients): per-GPU batch fixed, so scaling is weak.
 
-Rank 0 prints one JSON line.  `roofline` is for the dominant kernel: of the 5x5 206->206
+Rank 0 prints one JSON line.  With `--full`, `roofline` is for the dominant kernel: of the 5x5 206->206
 enhance_features_128 convolution's forward, input-gradient and weight-gradient kernels (each
 timed with HIP events around its launches on the launching stream during the timed steps), the
 one with the most time per step; `roofline_kernels` lists all three.  `cpu_baseline` times the
@@ -109,7 +119,14 @@ def parse():
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--img-size", type=int, default=None)
     ap.add_argument("--dtype", choices=["bf16", "fp16", "fp32"], default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the dominant-kernel probe (roofline, "
+                         "roofline_kernels) and the CPU baseline (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed path twice more from the run's initial weights and "
+                         "optimizer state and write what the second step returns (the loss dict) as "
+                         "DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="CPU baseline threads (default: OMP_NUM_THREADS, i.e. this process's CPU share -- 16 "
                          "on the GPU box, whose os.cpu_count() reports the whole host -- else os.cpu_count())")
@@ -187,6 +204,20 @@ def main():
                                        gradient_penalty=args.gp)
     B = args.batch
     batch = tpgan_train.synthetic_batch(B, dev, seed=1000 + rank, img_size=S)
+    # --dump-outputs: the state the run starts in, to run the dumped step from (see below)
+    initial = [{k: v.detach().clone() for k, v in net.state_dict().items()} if args.dump_outputs else None
+               for net in (G, D)]
+
+    def restore_initial():
+        """Both networks and their Adam states as they were before the first warm-up step (the
+        sequence of TPGANTrainer.load_checkpoint, from memory)."""
+        trainer._d_real_next = None  # (a D(real) pass precomputed with the trained weights)
+        for (_, net, flat), sd in zip(trainer._nets(), initial):
+            flat.load_optimizer_state_dict({"state": {}, "param_groups": []})  # step 0, zero moments
+            net.load_state_dict(sd)  # copies into the flat-buffer views
+            flat.weights_loaded()
+            flat.skipped.zero_()
+        torch.cuda.synchronize()
 
     # dominant-kernel probes: enhance_features_128 (206 -> 206, 5x5, at the full face size), its
     # forward, input gradient (the fused backward's first call: round 5 act links) and weight
@@ -230,7 +261,7 @@ def main():
         def run():
             return trainer.step(batch, next_b=batch)
 
-    if not graphed:
+    if args.full and not graphed:
         tpgan_ops.PROBE["match"] = match
         tpgan_ops.PROBE["events"] = []
     if world > 1:
@@ -261,6 +292,27 @@ def main():
         ex = torch.tensor([exposed["G"], exposed["D"]], dtype=torch.float64, device=dev)
         dist.all_reduce(ex, op=dist.ReduceOp.MAX)
         exposed["G"], exposed["D"] = float(ex[0]), float(ex[1])
+    if args.dump_outputs:
+        # The timed steps train: rounding differences between two runs (the tuner's picks, the order
+        # of atomic adds) grow with every Adam update, so the last timed step's losses differ from
+        # run to run.  The dump is therefore the timed path run twice more, outside the timed region,
+        # from the state this run started in (the seeded weights, zero Adam moments) on the same
+        # batch, and what the second step returns is written.  One step alone would not do: loss_D is
+        # taken before D's update and loss_G before G's backward, so G's backward and G's Adam (the
+        # dominant kernels) would reach neither.  The second step's losses are computed with the
+        # weights the whole first step produced, and depend on the arguments alone up to two steps'
+        # rounding.
+        if not graphed:
+            tpgan_ops.PROBE["match"] = None
+        restore_initial()
+        run()
+        dumped = run()
+        torch.cuda.synchronize()
+        if rank == 0:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, v in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), v.detach().float().cpu().numpy())
     ms_per_step = elapsed / args.steps * 1e3
     faces = world * B * args.steps / elapsed
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
@@ -270,10 +322,11 @@ def main():
     # dominant-kernel probe: HIP events around each launch on its launch stream.  Graph
     # nodes cannot be bracketed, so with graphs the probe runs eager steps right after the
     # timed region (same kernel, same shapes); eager runs probe the timed steps themselves.
-    if graphed:
+    # (--full only: a plain run times nothing but its steps, and `kern` below stays empty)
+    if args.full and graphed:
         tpgan_ops.PROBE["match"] = match
         tpgan_ops.PROBE["events"] = []
-    for _ in range(args.probe_steps if graphed else 0):
+    for _ in range(args.probe_steps if args.full and graphed else 0):
         trainer.step(batch)
     torch.cuda.synchronize()
     tpgan_ops.PROBE["match"] = None
@@ -302,7 +355,7 @@ def main():
         return
 
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         # the fixture-pinned CPU restatement (aten fp32) on the host cores, the
         # headline workload (full step incl. both Adam updates) at its batch and BASELINE
         # configs[0] at B=4, each one warm-up + median of --cpu-iters
@@ -389,6 +442,10 @@ def main():
                       "frac_of_peak": round(flops_step / (ms_per_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4)},
         "cpu_baseline": cpu,
     }
+    if not args.full:  # nothing was probed and no CPU step ran: the line carries no such figures
+        for k in ("roofline", "roofline_kernels", "cpu_baseline"):
+            del out[k]
+    out["full"] = args.full
     if world > 1:
         bst = trainer.bucket_stats()
         n_ex = max(exposed["steps"], 1)

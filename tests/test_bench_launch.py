@@ -46,6 +46,19 @@ def test_argv_gpus_and_launcher_cmd():
     assert bench.launch_ranks(["--gpus", "1"]) is None
 
 
+def test_plain_run_is_lean_by_default(monkeypatch):
+    """--full (kernel probes, CPU baseline) and --dump-outputs are off unless asked for."""
+    sys.path.insert(0, REPO)
+    import importlib
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", [BENCH, "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", [BENCH, "--full", "--dump-outputs", "out_dir"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out_dir"
+
+
 def test_gpus_mismatch_exits_nonzero():
     # one rank (WORLD_SIZE=1) told it is one of 2 GPUs: n_gpus would be misreported
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--no-cpu-baseline"], cwd=REPO,

@@ -52,6 +52,7 @@ def test_bench_gpus_flag_alone_launches_two_ranks(gpu):
 def test_bench_torchrun_two_ranks_one_gpu(gpu):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py")] + ARGS
+    cmd.append("--full")  # the kernel probes asserted below are measured only with --full
     env = dict(_rank_env(), MASTER_ADDR="127.0.0.1")
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=380)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]

@@ -9,8 +9,8 @@
 # fault, abort or time limit).
 #
 #   test [pytest args]     GPU suite: pytest -m gpu tests (or the given files / -k expression)
-#   bench [bench.py args]  headline bench (default --steps 20 --warmup 5 --no-cpu-baseline unless
-#                          args are given)
+#   bench [bench.py args]  headline bench with its kernel probes (default --full --steps 20 --warmup 5
+#                          --no-cpu-baseline unless args are given)
 #   prof [bench.py args]   rocprofv3 --kernel-trace --stats of the bench (+ tools/prof_summary.py)
 #   trace [args]           tools/trace_step.py (per-conv serialised layer times)
 #   layers [args]          tools/bench_layers.py
@@ -38,7 +38,7 @@ for spec in "$@"; do
   case $kind in
     test)  [[ ${#args[@]} -eq 0 ]] && args=(tests)
            cmd=(timeout -k 10 900 python -u -m pytest -m gpu -x -q --timeout 240 --timeout-method thread "${args[@]}") ;;
-    bench) [[ ${#args[@]} -eq 0 ]] && args=(--steps 20 --warmup 5 --no-cpu-baseline)
+    bench) [[ ${#args[@]} -eq 0 ]] && args=(--full --steps 20 --warmup 5 --no-cpu-baseline)
            cmd=(timeout -k 10 600 python -u bench.py "${args[@]}") ;;
     prof)  [[ ${#args[@]} -eq 0 ]] && args=(--steps 10 --warmup 5 --no-cpu-baseline)
            cmd=(timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d "$O/prof$i" -o run -- python3 bench.py "${args[@]}") ;;

@@ -39,7 +39,7 @@ def counters(d, kernel_sub, grid=None):
 def main():
     src, dst = sys.argv[1], sys.argv[2]
     os.makedirs(dst, exist_ok=True)
-    # bench line
+    # bench line (of a `bench.py --full` run: its roofline object is used below)
     with open(os.path.join(src, "bench.log")) as f:
         line = [ln for ln in f if ln.startswith("{")][-1]
     bench = json.loads(line)
