@@ -382,8 +382,11 @@ def test_train_step_with_gp_flat(gpu):
 
 def test_prepacked_weights_match_inline_packing(gpu):
     """After a train step the FlatParams-managed convs use pre-packed weight images
-    (tpg_pack_run after Adam); G / D outputs and input gradients match the per-call packing
-    path to within the run-to-run floor."""
+    (tpg_pack_run after Adam).  Default mode: G / D outputs and input gradients match the per-call
+    packing path to within the run-to-run floor.  Deterministic mode: three whole train steps from
+    one snapshot with the images and three with per-call packing land on the same weights and Adam
+    moments bit for bit, eager and as graph replays -- an image one update stale in any step moves
+    the next step's weights, so nothing but equality passes."""
     import tpgan_ops
     import tpgan_train
     G, D = _models(gpu)
@@ -432,47 +435,165 @@ def test_prepacked_weights_match_inline_packing(gpu):
         for h in hooks:
             h.remove()
     diff = [(n, rel(t2.cpu(), t0.cpu())) for (n, t0), (_, t2) in zip(a[3], c[3]) if rel(t2.cpu(), t0.cpu()) > 1e-6][:6]
+    failures = []  # (both halves always run: the default-mode verdict is given at the end)
     for i in range(3):
         floor = rel(a2[i].cpu(), a[i].cpu())
-        assert rel(c[i].cpu(), a[i].cpu()) <= max(3 * floor, 1e-6), (i, rel(c[i].cpu(), a[i].cpu()), floor, diff)
+        if not rel(c[i].cpu(), a[i].cpu()) <= max(3 * floor, 1e-6):
+            failures.append(("default mode", i, rel(c[i].cpu(), a[i].cpu()), floor, diff))
+    del a, a2, c, calls
+
+    # ---- deterministic mode: whole trajectories.  Both paths take the same plans there (no data
+    # split tuner, no split-K; the weight-gradient picks come from the one shared cache), so the
+    # only difference left is who wrote the 16-bit weight image
+    def state():
+        torch.cuda.synchronize()
+        return [t.clone() for f in (tr.fG, tr.fD) for t in (f.data, f.exp_avg, f.exp_avg_sq)]
+
+    with tpgan_ops.deterministic():
+        tr.step(b)
+        torch.cuda.synchronize()
+        snap = _snapshot(tr)
+        got = {}
+        for graphed in (False, True):
+            for pack in (True, False):
+                tpgan_ops.PACK["enabled"] = pack
+                try:
+                    _restore(tr, snap)
+                    if graphed:
+                        tr.reset_capture()
+                        tr.capture(b, warmup=0)
+                        _restore(tr, snap)
+                    for _ in range(3):
+                        tr.step_graphed() if graphed else tr.step(b)
+                    got[(graphed, pack)] = state()
+                finally:
+                    tpgan_ops.PACK["enabled"] = True
+        tr.reset_capture()
+    assert not torch.equal(got[(False, True)][0], snap[0])  # (the steps did move the weights)
+    tnames = ("fG.data", "fG.exp_avg", "fG.exp_avg_sq", "fD.data", "fD.exp_avg", "fD.exp_avg_sq")
+    for graphed in (False, True):
+        for n, x, y in zip(tnames, got[(graphed, True)], got[(graphed, False)]):
+            if not torch.equal(x, y):
+                failures.append(("deterministic, %s: pre-packed vs inline" % ("graph replays" if graphed else "eager"), n,
+                                 rel(x.cpu(), y.cpu())))
+    assert not failures, failures
+
+
+def _images_current(tr, tag):
+    """Every pre-packed image of G and D is at its network's epoch and equals a from-scratch pack
+    (fresh jobs, new buffer) of the LIVE parameter found at the entry's source pointer; an entry
+    whose pointer matches no live parameter fails by name.  Returns the number checked."""
+    import tpgan_ops
+    from _packcheck import check_entries
+    return sum(check_entries(tpgan_ops, f, f.params, tag + "/" + n) for n, f in (("G", tr.fG), ("D", tr.fD)))
 
 
 def test_prepacked_images_current_after_steps(gpu):
     """Every pre-packed weight image of G and D equals a fresh pack of the current fp32 weights
-    after eager steps and after graph replays (no entry left out of the batched re-pack, none
-    packed from a stale or foreign weight pointer): each entry's own jobs are re-run and the
-    image must not change, bit for bit."""
-    import tpgan_ops
+    after eager steps, after a restore (weights_loaded) and after graph replays: no entry left
+    out of the batched re-pack, none packed from a stale or foreign weight pointer.  The fresh
+    pack is planned from the live parameter view, not from the entry's stored jobs (re-running
+    those proves nothing about where they read from)."""
     import tpgan_train
     G, D = _models(gpu)
     tr = tpgan_train.TPGANTrainer(G, D, compute_dtype=torch.bfloat16, use_dropout=False)
     b = tpgan_train.synthetic_batch(2, gpu, seed=29)
-    lib = tpgan_ops.load()
-
-    def check_images(tag):
-        torch.cuda.synchronize()
-        n = 0
-        for flat in (tr.fG, tr.fD):
-            for key, e in flat.pack_entries.items():
-                if e is None or not e.njobs:
-                    continue
-                assert e.epoch == flat.epoch, (tag, key[0], key[1][:9], e.epoch, flat.epoch)
-                before = e.buf.clone()
-                tpgan_ops.check(lib.tpg_pack_run(e.dev.data_ptr(), e.njobs, e.nblocks, tpgan_ops.stream_ptr()))
-                torch.cuda.synchronize()
-                assert torch.equal(before, e.buf), (tag, key[0], key[1][:9])
-                n += 1
-        return n
-
     for _ in range(3):
         tr.step(b)
-    assert check_images("eager") > 50
+    assert _images_current(tr, "eager") > 50
+    snap = _snapshot(tr)
+    tr.step(b)
+    _restore(tr, snap)
+    assert _images_current(tr, "restored") > 50
     tr.capture(b, warmup=1)
     for _ in range(2):
         tr.step_graphed()
-    assert check_images("graph") > 50
+    assert _images_current(tr, "graph") > 50
 
 
+def test_prepacked_images_current_bucketed_optimizer(gpu):
+    """The same with overlap_optimizer=True: G's images re-packed bucket by bucket on the
+    communication stream (repack_range), through the step that re-lays the flat buffers out
+    (every image dropped and rebuilt at the parameters' new addresses), a restore, and a
+    capture."""
+    import tpgan_train
+    G, D = _models(gpu)
+    tr = tpgan_train.TPGANTrainer(G, D, compute_dtype=torch.bfloat16, use_dropout=False, overlap_optimizer=True)
+    assert tr.gsync is not None and tr.gsync.optimizer is not None
+    b = tpgan_train.synthetic_batch(2, gpu, seed=29)
+    tr.step(b)  # learns the bucket order and re-lays G's buffers out
+    assert tr.fG.layout_version == 1 and not any(e is not None for e in tr.fG.pack_entries.values())
+    tr.step(b)  # the first step on the new layout: every G image is new
+    assert _images_current(tr, "relaid") > 50
+    tr.step(b)
+    assert tr.fG.range_packs[1] and _images_current(tr, "bucketed") > 50
+    snap = _snapshot(tr)
+    tr.step(b)
+    _restore(tr, snap)
+    assert _images_current(tr, "restored") > 50
+    tr.capture(b, warmup=1)
+    for _ in range(2):
+        tr.step_graphed()
+    assert _images_current(tr, "graph") > 50
+
+
+def _ledger_check(events, first_clean, tag):
+    """events: one list of ledger lines per step.  No lazy pack from step `first_clean` on; and a
+    lazily packed image is read, for as long as it stays at that epoch, on the stream that packed
+    it (a read on another stream has no ordering against the pack unless somebody put one there)."""
+    for s, evs in enumerate(events[first_clean:], first_clean):
+        lazy = [(e[1][0], e[1][1][:9]) for e in evs if e[0] == "lazy"]
+        assert not lazy, (tag, "step %d packs on use" % s, len(lazy), lazy[:4])
+    flat = [e for evs in events for e in evs]
+    packed_on = {}
+    for kind, key, stream, fepoch, eepoch in flat:
+        if kind == "lazy":
+            packed_on[(key, eepoch)] = stream
+        elif kind in ("batched", "range"):
+            packed_on.pop((key, eepoch), None)  # (re-packed by the optimizer: no longer the lazy image)
+        elif kind == "read" and (key, eepoch) in packed_on:
+            assert stream == packed_on[(key, eepoch)], (
+                tag, "image packed on use on stream %#x is read on stream %#x" % (packed_on[(key, eepoch)], stream),
+                key[0], key[1][:9], eepoch)
+    return sum(1 for e in flat if e[0] == "lazy"), sum(1 for e in flat if e[0] == "read")
+
+
+def test_pack_ledger_stream_order(gpu, monkeypatch):
+    """tpgan_ops.PACK["audit"] over four eager steps (side-stream local pathways, the identity
+    fork) and over capture()'s warm-up on its side stream: which stream packed each image and
+    which streams read it."""
+    import FeatureExtract as FE
+    import tpgan_ops
+    import tpgan_train
+    assert tpgan_ops.MULTISTREAM and tpgan_train.IDENTITY_STREAM["enabled"]
+    G, D = _models(gpu)
+    torch.manual_seed(0)
+    ext = FE.FeatureExtractModel("mobilenetv2", 347).to(gpu)
+    tr = tpgan_train.TPGANTrainer(G, D, lr=LR, betas=BETAS, compute_dtype=torch.bfloat16, use_dropout=False,
+                                  identity_fn=FE.IdentityPreservingLoss(ext, torch.bfloat16))
+    b = tpgan_train.synthetic_batch(2, gpu, seed=31)
+    audit = []
+    monkeypatch.setitem(tpgan_ops.PACK, "audit", audit)
+    events, relaid = [], -1
+    for s in range(4):
+        n0, lv = len(audit), (tr.fG.layout_version, tr.fD.layout_version)
+        tr.step(b)
+        torch.cuda.synchronize()
+        events.append(audit[n0:])
+        if (tr.fG.layout_version, tr.fD.layout_version) != lv:
+            relaid = s
+    first_clean = relaid + 2  # the second step after the last relayout (none: after construction)
+    assert first_clean <= 2, relaid
+    nlazy, nread = _ledger_check(events, first_clean, "eager")
+    print("ledger, eager: %d lazy packs, %d reads, %d streams" % (nlazy, nread, len({e[2] for e in audit})))
+    assert nlazy > 50 and nread > 4 * 50  # (the first step did pack on use, every step reads)
+    assert len({e[2] for e in audit if e[0] == "read"}) > 1  # (the side streams are in the ledger)
+    assert any(e[0] == "batched" for e in audit)
+    # capture()'s warm-up steps run on a side stream of its own; every image is current by now
+    n0 = len(audit)
+    tr.capture(b, warmup=2, segmented=True)
+    torch.cuda.synchronize()
+    _ledger_check(events + [audit[n0:]], len(events), "capture warm-up")
 def test_deterministic_mode_bit_identical(gpu):
     """tpg_set_deterministic: two bf16 train steps from the same state give bit-identical
     parameters, gradients and Adam moments (SURVEY.md §5 race detection / run-to-run)."""

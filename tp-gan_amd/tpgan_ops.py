@@ -491,11 +491,36 @@ def _tuned_wgrad(lib, d, x, g, dwv):
 # update instead of inside every fwd / dgrad call: each (parameter, op, shape) gets a
 # persistent packed image; FlatParams.adam() repacks every image of its network with ONE
 # batched launch (tpg_pack_run) right after the Adam launch.
-PACK = {"enabled": True}
+# PACK["audit"]: None, or a list that _packed_weight / repack / repack_range append
+# (kind, entry key, stream id, flat.epoch, entry.epoch) to -- kind "lazy" (packed on use), "batched"
+# (repack), "range" (repack_range) or "read" (the image handed to a conv); both epochs as they
+# stand after the event.  Host list appends only: legal inside a graph capture.
+# PACK["fallbacks"]: calls that had a packed image and were refused it (-21), re-run packing inline.
+PACK = {"enabled": True, "audit": None, "fallbacks": 0}
 
 
 class _PackEntry:
-    __slots__ = ("buf", "jobs", "njobs", "dev", "nblocks", "epoch")
+    # desc / op / src / strides / shape: what the image was planned and packed from (a copy of the
+    # descriptor as it stood at pack time, flags / data_algo / data_ksplit included, and the fp32
+    # source view), enough to rebuild it from scratch
+    __slots__ = ("buf", "jobs", "njobs", "dev", "nblocks", "epoch", "key", "desc", "op", "src", "strides", "shape")
+
+
+def _src_in_flat(flat, e):
+    """An entry's fp32 source [src, src + numel * 4) must lie inside its network's current flat
+    buffer (holders without one, _FrozenPack, are exempt): an image packed from anywhere else
+    follows no update of that buffer."""
+    data = getattr(flat, "data", None)
+    if data is None:
+        return
+    base = data.data_ptr()
+    nel = 1
+    for s_ in e.shape:
+        nel *= s_
+    if not (base <= e.src and e.src + 4 * nel <= base + 4 * data.numel()):
+        raise RuntimeError("packed weight image (op %d, weight %s, %s): its source [%#x, %#x) is outside the flat "
+                           "parameter buffer [%#x, %#x)" % (e.op, tuple(e.shape), desc_key(e.desc), e.src,
+                                                            e.src + 4 * nel, base, base + 4 * data.numel()))
 
 
 def _pack_entry(flat, key, d, op, w):
@@ -509,6 +534,9 @@ def _pack_entry(flat, key, d, op, w):
         return None
     jb = lib.tpg_pack_job_bytes()
     e = _PackEntry()
+    e.key, e.op, e.desc = key, op, ConvDesc.from_buffer_copy(d)
+    e.src, e.strides, e.shape = w.data_ptr(), tuple(w.stride()), tuple(w.shape)
+    _src_in_flat(flat, e)
     e.buf = torch.empty(nb, dtype=torch.uint8, device=w.device)
     host = ctypes.create_string_buffer(jb * 64)
     n = lib.tpg_conv2d_pack_jobs(ctypes.byref(d), op, tt(w), e.buf.data_ptr(), host, 64)
@@ -532,14 +560,22 @@ def _packed_weight(param, d, op, w):
     flat = getattr(param, "_tpg_flat", None)
     if flat is None or not PACK["enabled"] or d.dtype == TPG_F32 or w.dtype != torch.float32:
         return None
+    # (flags / data_algo / data_ksplit are not in the key: the image's layout follows the shape and
+    # dtype alone, only the launch plan follows them -- tests/test_pack_host.py pins that on the
+    # pack jobs, tests/test_gpu_pack.py on the images and the results)
     key = (op, _desc_tuple(d), w.data_ptr(), tuple(w.stride()))
     e = _pack_entry(flat, key, d, op, w)
     if e is None:
         return None
+    aud = PACK["audit"]
     if e.epoch != flat.epoch:
         if e.njobs:
             check(load().tpg_pack_run(e.dev.data_ptr(), e.njobs, e.nblocks, stream_ptr()))
         e.epoch = flat.epoch
+        if aud is not None:
+            aud.append(("lazy", key, stream_ptr().value or 0, flat.epoch, e.epoch))
+    if aud is not None:
+        aud.append(("read", key, stream_ptr().value or 0, flat.epoch, e.epoch))
     return e.buf
 
 
@@ -549,6 +585,13 @@ def repack(flat):
     if not entries:
         return
     lib = load()
+    # every source still inside flat.data: checked when the table is (re)built and whenever the
+    # buffer is not the one the last check saw (an entry's source never changes)
+    where = (flat.data.data_ptr(), flat.data.numel())
+    if flat.pack_table is None or getattr(flat, "pack_checked", None) != where:
+        for e in entries:
+            _src_in_flat(flat, e)
+        flat.pack_checked = where
     if flat.pack_table is None:
         raw = b"".join(e.jobs for e in entries)
         n = sum(e.njobs for e in entries)
@@ -559,6 +602,10 @@ def repack(flat):
     check(lib.tpg_pack_run(dev.data_ptr(), n, nblocks, stream_ptr()))
     for e in entries:
         e.epoch = flat.epoch
+    aud = PACK["audit"]
+    if aud is not None:
+        st = stream_ptr().value or 0  # (the null stream reads as None)
+        aud.extend(("batched", e.key, st, flat.epoch, e.epoch) for e in entries)
 
 
 def _packed_tt(buf, dtype=TPG_BF16):
@@ -579,6 +626,7 @@ def _run_maybe_packed(fn_packed, fn_plain, d, pk):
         if rc != -21:
             check(rc)
             return
+        PACK["fallbacks"] += 1
     check(fn_plain())
 
 
@@ -1729,6 +1777,8 @@ def repack_range(flat, off, n, epoch):
         base = flat.data.data_ptr()
         entries = [e for k, e in flat.pack_entries.items()
                    if e is not None and e.njobs and off <= (k[2] - base) // 4 < off + n]
+        for e in entries:
+            _src_in_flat(flat, e)
         if entries:
             raw = b"".join(e.jobs for e in entries)
             nj = sum(e.njobs for e in entries)
@@ -1743,6 +1793,10 @@ def repack_range(flat, off, n, epoch):
         check(lib.tpg_pack_run(dev.data_ptr(), nj, nblocks, stream_ptr()))
     for e in entries:
         e.epoch = epoch
+    aud = PACK["audit"]
+    if aud is not None:
+        st = stream_ptr().value or 0  # (the null stream reads as None)
+        aud.extend(("range", e.key, st, flat.epoch, e.epoch) for e in entries)
 
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, state, step=0, grad_scale=1.0):
