@@ -151,6 +151,36 @@ int32_t tpg_conv2d_bwd_data(const tpg_conv_desc* d, tpg_tensor g, tpg_tensor w, 
 int32_t tpg_conv2d_bwd_filter(const tpg_conv_desc* d, tpg_tensor x, tpg_tensor g, tpg_tensor dw,
                               void* ws, size_t ws_bytes, tpg_stream_t stream);
 
+/* The plan tpg_conv2d_bwd_filter (and step 3 of tpg_conv2d_bwd) runs for these tensors: host
+ * arithmetic on the descriptor, dtypes, strides and pointer alignment only -- no device work,
+ * nothing dereferenced, nothing launched or flushed.  Returns what tpg_conv2d_bwd_filter would
+ * return before its first launch (0, or e.g. -30 for a desc.algo that does not cover the shape;
+ * *out is then untouched).  Reads the same process state as the launch: desc.flags CONCURRENT,
+ * tpg_set_deterministic, TPG_RH_SKIP. */
+enum { TPG_WGRAD_GENERIC = 0, TPG_WGRAD_FLAT = 1, TPG_WGRAD_ROW_HALO = 2, TPG_WGRAD_IMAGE_HALO = 3 };
+enum {
+  TPG_WGRAD_SUMS_BIAS = 1, /* the launch adds the bias gradient when given one (tpg_conv2d_bwd) */
+  TPG_WGRAD_BFLAT = 2,     /* flat kernel: columns flattened over taps */
+  TPG_WGRAD_FASTP = 4,     /* flat kernel: division-free addressing of the pixel-grid operand */
+  TPG_WGRAD_FASTQ = 8,     /* flat kernel: the same for the gathered operand */
+  TPG_WGRAD_SKIP = 16,     /* halo kernels: MFMAs of all-padding blocks of edge tiles skipped */
+  TPG_WGRAD_GROUPED = 32   /* recorded, not launched, inside a launch group (tpg_group_begin) */
+};
+typedef struct tpg_wgrad_plan {
+  int32_t kernel;          /* TPG_WGRAD_*: generic (tpg_wgrad.hip), flat DMA (tpg_wgrad2.hip), kernel-row
+                              halo or image halo (tpg_wgrad_rh.hip) */
+  int32_t cfg;             /* the kernel family's own tile index */
+  int32_t tile_m, tile_n;  /* tile: a channels x b columns */
+  int32_t splits;          /* pixel splits (1: every dW element added once) */
+  int32_t per_split;       /* pixels per split (generic, flat) or 64-pixel k-tiles per split (halo) */
+  int32_t tiles;           /* output tiles; the grid is tiles x splits blocks */
+  int32_t taps_per_block;  /* halo kernels: kernel rows x taps one block accumulates; else 0 */
+  int32_t bias_share;      /* column tiles the bias sums are spread over (0: generic kernel) */
+  int32_t flags;           /* TPG_WGRAD_SUMS_BIAS | ... */
+} tpg_wgrad_plan;
+int32_t tpg_conv2d_wgrad_plan(const tpg_conv_desc* d, tpg_tensor x, tpg_tensor g, tpg_tensor dw,
+                              tpg_wgrad_plan* out);
+
 /* Fused per-layer backward of tpg_conv2d_fwd's op (replaces aten convolution_backward of the
  * nn.Conv2d / nn.ConvTranspose2d built at ModificationLayer.py:101 / :186, plus the activation
  * backward of the layer's LeakyReLU / ReLU):

@@ -125,6 +125,39 @@ def test_null_tensor_rejected_without_device_work(lib):
     assert rc < 0 and b"NULL" in lib.tpg_last_error()
 
 
+def test_wgrad_plans_match_recorded(lib):
+    """tpg_conv2d_wgrad_plan returns, for every row of tests/golden/wgrad_plans.json, exactly the
+    recorded status or plan (kernel, tile, pixel split, tiles, taps per block, bias share, flags).
+    The fixture is a record of the planner's picks -- TP-GAN's layer shapes, the GPU tests'
+    weight-gradient geometries and a random walk, over dtypes, layouts, CONCURRENT,
+    deterministic mode and every tuner pick -- first taken from the code before planning and
+    launching were split.  It is regenerated (tests/golden/make_wgrad_plans.py) only by a
+    change that means to move a plan."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("make_wgrad_plans",
+                                                  os.path.join(REPO, "tests", "golden", "make_wgrad_plans.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    fx = json.load(open(os.path.join(REPO, "tests", "golden", "wgrad_plans.json")))
+    assert tuple(fx["shape_fields"]) == gen.SHAPE_FIELDS and tuple(fx["plan_fields"]) == gen.PLAN_FIELDS
+    assert len(fx["rows"]) > 4000
+    bad = []
+    for r in fx["rows"]:
+        got = gen.query(L, lib, fx["shapes"][r[0]], *r[1:7])
+        if got != r[7:]:
+            bad.append((fx["shapes"][r[0]], r[1:7], "recorded", r[7:], "got", got))
+    assert not bad, "%d of %d plans moved, first: %s" % (len(bad), len(fx["rows"]), bad[:3])
+    # a failing status leaves the caller's struct alone and sets the message
+    d = _desc(32, 64, 128, 128, 64, 5, 2, 2)
+    d.algo, d.ksplit = 6, 1
+    x, g = gen._act(L, 64, 128, 128, L.TPG_BF16, 0), gen._act(L, 64, 64, 64, L.TPG_BF16, 0)
+    dw = gen._act(L, 64, 5, 5, L.TPG_F32, 1)
+    plan = L.WgradPlan(kernel=-7)
+    assert lib.tpg_conv2d_wgrad_plan(ctypes.byref(d), x, g, dw, ctypes.byref(plan)) == -30
+    assert plan.kernel == -7 and b"row-halo kernel does not apply" in lib.tpg_last_error()
+
+
 def test_planner_sanitizer_sweep():
     """The planner (descriptor validation, plans, workspace and pre-pack sizing) rebuilt with
     host AddressSanitizer + UBSan and driven over TP-GAN's layer shapes, a seeded random walk of

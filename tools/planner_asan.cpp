@@ -1,6 +1,6 @@
 // Host-side AddressSanitizer sweep of the convolution planner (tpg_capi.hip).
 //
-// The planner (check_desc -> plan_fwd / plan_bwd_data / maybe_halo / wgrad tile choice ->
+// The planner (check_desc -> plan_fwd / plan_bwd_data / maybe_halo / plan_bwd_filter ->
 // workspace and pre-pack sizing) is pure host code: it runs before any launch and sizes the
 // buffers every kernel later indexes, so an out-of-range tap table, a vector overrun or a
 // wrong region size shows up here first.  This driver feeds it a deterministic sweep of
@@ -9,9 +9,11 @@
 // every entry point that does no device work:
 //   tpg_conv2d_workspace (all three ops and out-of-range op codes),
 //   tpg_conv2d_packed_bytes, tpg_conv2d_pack_jobs (host job table only), tpg_pack_prepare,
+//   tpg_conv2d_wgrad_plan (the weight gradient's kernel / tile / pixel-split choice and
+//   argument fill, on four tensor layouts per valid descriptor; the plan must be consistent),
 //   and the launch entry points with descriptors check_desc rejects (validation path only).
 // Built with `make -C tp-gan_amd asan` (planner object compiled with -fsanitize=address on
-// the host side only; the kernels are the product's) and run by tests/test_host_logic.py.
+// the host side only; the kernels are the product's) and run by tests/test_capi.py.
 // Exit status: 0 clean, 1 a consistency check failed; ASan aborts on a memory error.
 #include <cstdint>
 #include <cstdio>
@@ -29,7 +31,63 @@ static uint32_t rnd() {
 static int pick(const int* v, int n) { return v[rnd() % n]; }
 
 static int g_fail = 0;
-static long g_valid = 0, g_rejected = 0, g_jobs = 0;
+static long g_valid = 0, g_rejected = 0, g_jobs = 0, g_plans = 0;
+
+// channels-last activation of a never-dereferenced buffer, in the layouts of
+// tests/golden/make_wgrad_plans.py: 0 channels padded to 8, 1 as they are, 2 a view narrower
+// than its buffer, 3 a batch stride of 2^30 elements (byte extent past 2^31)
+static tpg_tensor fake_act(int c, int h, int w, int dtype, int layout) {
+  tpg_tensor t;
+  memset(&t, 0, sizeof(t));
+  const int64_t cp = layout == 1 ? c : (c + 7) / 8 * 8, row = (w + (layout == 2 ? 2 : 0)) * cp;
+  t.data = (void*)0x10000;
+  t.dtype = dtype;
+  t.stride[0] = h * row; t.stride[1] = 1; t.stride[2] = row; t.stride[3] = cp;
+  if (layout == 3 && t.stride[0] < (1ll << 30)) t.stride[0] = 1ll << 30;
+  return t;
+}
+
+// The weight-gradient plan of a valid descriptor (its own algo / ksplit / flags) in every
+// layout: tile cost models, the pixel-split model, byte extents and the argument fill all run
+// here, and the plan that comes back must be one a launch could use.
+static void check_wgrad_plans(const tpg_conv_desc* d) {
+  for (int layout = 0; layout < 4; ++layout) {
+    const tpg_tensor x = fake_act(d->in_c, d->in_h, d->in_w, d->dtype, layout);
+    const tpg_tensor g = fake_act(d->out_c, d->out_h, d->out_w, d->dtype, layout);
+    const int b = d->transposed ? d->out_c : d->in_c;
+    tpg_tensor dw = fake_act(b, d->kh, d->kw, TPG_F32, 1);
+    tpg_wgrad_plan* p = (tpg_wgrad_plan*)malloc(sizeof(tpg_wgrad_plan));
+    const int32_t rc = tpg_conv2d_wgrad_plan(d, x, g, dw, p);
+    ++g_plans;
+    const char* why = nullptr;
+    if (rc == 0) {
+      const bool halo = p->kernel == TPG_WGRAD_ROW_HALO || p->kernel == TPG_WGRAD_IMAGE_HALO;
+      const int PH = d->transposed ? d->in_h : d->out_h, PW = d->transposed ? d->in_w : d->out_w;
+      // what the splits must cover: pixels of the iteration grid (1 x 1 in the GEMM forms), or
+      // the halo kernels' 64-pixel k-tiles of (64 / tw) rows of tw = min(width, 64) pixels
+      const int tw = p->kernel == TPG_WGRAD_IMAGE_HALO && PW < 64 ? PW : 64;
+      const int64_t need = halo ? (int64_t)d->n * ((PH + 64 / tw - 1) / (64 / tw)) * (PW / tw) : (int64_t)d->n * PH * PW;
+      const int64_t have = (int64_t)p->per_split * p->splits;
+      if (p->kernel < TPG_WGRAD_GENERIC || p->kernel > TPG_WGRAD_IMAGE_HALO) why = "kernel kind out of range";
+      else if (p->splits < 1) why = "splits < 1";
+      else if (p->tiles < 1) why = "tiles < 1";
+      else if (p->tile_m < 1 || p->tile_n < 1) why = "empty tile";
+      else if (have < need) why = "splits do not cover the pixels";
+      else if (halo && (d->dtype == TPG_F32 || d->stride_h != 1 || d->stride_w != 1 || d->transposed))
+        why = "halo kernel for an fp32, strided or transposed conv";
+      else if (halo != (p->taps_per_block > 0)) why = "taps_per_block disagrees with the kernel kind";
+    } else if (rc != -30 && rc != -4) {
+      why = "unexpected status";
+    }
+    if (why) {
+      fprintf(stderr, "wgrad plan (layout %d, rc %d): %s: n=%d c=%d->%d %dx%d->%dx%d k=%dx%d s=%d,%d T=%d dt=%d algo=%d ks=%d fl=%d: %s\n",
+              layout, rc, why, d->n, d->in_c, d->out_c, d->in_h, d->in_w, d->out_h, d->out_w, d->kh, d->kw, d->stride_h,
+              d->stride_w, d->transposed, d->dtype, d->algo, d->ksplit, d->flags, rc ? tpg_last_error() : "");
+      g_fail = 1;
+    }
+    free(p);
+  }
+}
 
 static void run_one(const tpg_conv_desc& d0, bool expect_valid) {
   // the descriptor is copied to a heap block of exactly its size so a read past it is caught
@@ -75,6 +133,7 @@ static void run_one(const tpg_conv_desc& d0, bool expect_valid) {
     (void)tpg_conv2d_pack_jobs(d, op, wt, wp, jobs, 0);
     free(jobs);
   }
+  if (ok) check_wgrad_plans(d);
   if (!ok) {  // launch entry points must stop at validation (no device work happens)
     tpg_tensor z;
     memset(&z, 0, sizeof(z));
@@ -192,7 +251,7 @@ int main(int argc, char** argv) {
     run_one(d, valid && d.kh <= 7 && d.kw <= 7 && d.out_h > 0 && d.out_w > 0 && d.in_h > 0);
   }
   (void)tpg_conv2d_workspace(nullptr, TPG_OP_FWD);
-  printf("planner_asan: %ld valid, %ld rejected descriptors, %ld pack jobs, %s\n", g_valid, g_rejected, g_jobs,
-         g_fail ? "FAILED" : "ok");
+  printf("planner_asan: %ld valid, %ld rejected descriptors, %ld pack jobs, %ld wgrad plans, %s\n", g_valid, g_rejected,
+         g_jobs, g_plans, g_fail ? "FAILED" : "ok");
   return g_fail;
 }

@@ -1100,11 +1100,23 @@ static int32_t bwd_data_impl(const tpg_conv_desc* d, tpg_tensor g, tpg_tensor w,
                    "reflect_fold");
 }
 
-// Row-halo weight gradient (tpg_wgrad_rh.hip) for a stride-1 Conv2d: returns 1 when the
-// shape is not covered (caller falls back), else the launch status.
-static int32_t wgrad_rh(const tpg_conv_desc* d, const tpg_tensor& x, const tpg_tensor& g, const tpg_tensor& dw,
-                        float* dbias, hipStream_t stream) {
-  if (!half16(d->dtype) || d->stride_h != 1 || d->stride_w != 1) return 1;
+// ---- weight-gradient plans: kernel family, tile, pixel split and every launch argument that
+// needs no data pointer.  Host arithmetic on the descriptor, dtypes and strides only (no
+// launch, no launch-group flush, no HIP call); run_wgrad adds the pointers and launches.
+struct WgradPlan {
+  int kernel;       // TPG_WGRAD_*
+  int cfg, bm, bn, tiles;
+  bool sums_bias;   // the launch adds dbias when given one
+  bool p_is_x;      // iteration-grid operand P: x (ConvTranspose2d) or g
+  WgradArgs a;      // generic and flat kernels
+  WgradRHArgs rh;   // row- and image-halo kernels
+};
+
+// Row-halo weight gradient (tpg_wgrad_rh.hip) for a stride-1 Conv2d: false when the shape is
+// not covered (the caller falls back).
+static bool plan_wgrad_rh(const tpg_conv_desc* d, const tpg_tensor& x, const tpg_tensor& g, const tpg_tensor& dw,
+                          WgradPlan* p) {
+  if (!half16(d->dtype) || d->stride_h != 1 || d->stride_w != 1) return false;
   const int PH = d->out_h, PW = d->out_w, QH = d->in_h, QW = d->in_w;
   // row mode: one kernel row, 3/5/7 taps, 64-pixel row segments; image mode (algos 10, 11 and
   // the default below 64 pixels of width): all taps of a 2x2 / 3x3 kernel from one halo of
@@ -1117,22 +1129,21 @@ static int32_t wgrad_rh(const tpg_conv_desc* d, const tpg_tensor& x, const tpg_t
                       (63 / tw + d->kh - 1) * (tw + d->kw - 1) + tw + d->kw - 2 < 200;
   // (untuned default only for full 64-pixel k-tiles: 40-wide maps measured slower than wgrad2)
   const bool img = d->algo == 10 || d->algo == 11 || (d->algo == 0 && !row_ok && 64 % tw == 0);
-  if (img ? !img_ok : !row_ok) return 1;
-  if (d->pad_t >= QH || d->pad_l >= QW || !vec_ok(g, d->dtype) || !vec_ok(x, d->dtype)) return 1;
-  if (g.stride[2] != (int64_t)PW * g.stride[3] || g.stride[0] != (int64_t)PH * g.stride[2]) return 1;
-  if (x.stride[2] != (int64_t)QW * x.stride[3] || x.stride[0] != (int64_t)QH * x.stride[2]) return 1;
+  if (img ? !img_ok : !row_ok) return false;
+  if (d->pad_t >= QH || d->pad_l >= QW || !vec_ok(g, d->dtype) || !vec_ok(x, d->dtype)) return false;
+  if (g.stride[2] != (int64_t)PW * g.stride[3] || g.stride[0] != (int64_t)PH * g.stride[2]) return false;
+  if (x.stride[2] != (int64_t)QW * x.stride[3] || x.stride[0] != (int64_t)QH * x.stride[2]) return false;
   // extents cover the last pixel's whole 16-byte chunks (vec_ok: pixel stride >= ceil8(C))
   const int64_t pb = ((int64_t)(d->n - 1) * g.stride[0] + (int64_t)(PH - 1) * g.stride[2] +
                       (int64_t)(PW - 1) * g.stride[3] + rup(d->out_c, 8)) * 2;
   const int64_t qb = ((int64_t)(d->n - 1) * x.stride[0] + (int64_t)(QH - 1) * x.stride[2] +
                       (int64_t)(QW - 1) * x.stride[3] + rup(d->in_c, 8)) * 2;
-  if (pb >= (1ll << 31) || qb >= (1ll << 31)) return 1;
-  WgradRHArgs a;
-  memset(&a, 0, sizeof(a));
+  if (pb >= (1ll << 31) || qb >= (1ll << 31)) return false;
+  WgradRHArgs& a = p->rh;
   a.dtype = d->dtype;
-  a.P = g.data; a.p_sn = (int)g.stride[0]; a.p_sh = (int)g.stride[2]; a.p_sw = (int)g.stride[3];
+  a.p_sn = (int)g.stride[0]; a.p_sh = (int)g.stride[2]; a.p_sw = (int)g.stride[3];
   a.PH = PH; a.PW = PW; a.Ca = d->out_c; a.p_bytes = (int)pb;
-  a.Q = x.data; a.q_sn = (int)x.stride[0]; a.q_sh = (int)x.stride[2]; a.q_sw = (int)x.stride[3];
+  a.q_sn = (int)x.stride[0]; a.q_sh = (int)x.stride[2]; a.q_sw = (int)x.stride[3];
   a.QH = QH; a.QW = QW; a.Cb = d->in_c; a.q_bytes = (int)qb;
   a.kh = d->kh; a.kw = d->kw; a.pt = d->pad_t; a.pl = d->pad_l; a.pad_mode = d->pad_mode;
   a.nr = img ? d->kh : 1;
@@ -1180,30 +1191,28 @@ static int32_t wgrad_rh(const tpg_conv_desc* d, const tpg_tensor& x, const tpg_t
   if (deterministic()) ks = 1;  // one block adds each dW element once
   a.kt_per_split = cdiv(a.nkt, ks);
   a.ksplit = cdiv(a.nkt, a.kt_per_split);
-  a.dW = reinterpret_cast<float*>(dw.data);
   a.w_sa = dw.stride[0]; a.w_sb = dw.stride[1]; a.w_sr = dw.stride[2]; a.w_ss = dw.stride[3];
-  a.dbias = dbias;
   // bias MFMAs spread over up to 16 / ksplit tiles: same-address atomics serialise (~50 ns
   // each), so blocks x splits adding into one dbias row must stay few
   a.bshare = deterministic() ? 1 : std::max(1, std::min(a.ntb * a.nrg * cdiv(a.kw, a.nt), 16 / a.ksplit));
   a.skip = g_rh_skip;
-  TPG_GROUP_SYNC();
-  return hip_check(launch_wgrad_rh(a, stream), "wgrad_rh");
+  p->kernel = img ? TPG_WGRAD_IMAGE_HALO : TPG_WGRAD_ROW_HALO;
+  p->cfg = a.cfg; p->bm = bm; p->bn = bc; p->tiles = a.tiles;
+  return true;
 }
 
-// Weight gradient; with dbias (Conv2d only: the pixel-grid operand is g) the bias gradient is
-// summed by the same launch where the kernel supports it (*bias_done), else left to the caller.
-static int32_t bwd_filter_impl(const tpg_conv_desc* d, const tpg_tensor& x, const tpg_tensor& g, const tpg_tensor& dw,
-                               float* dbias, bool* bias_done, tpg_stream_t stream) {
+// Validates the call and plans it: the row/image-halo kernel where it applies (desc.algo 0 or
+// 6..12), else the flat DMA kernel on 16-byte aligned rows, else the generic kernel.
+static int32_t plan_bwd_filter(const tpg_conv_desc* d, const tpg_tensor& x, const tpg_tensor& g, const tpg_tensor& dw,
+                               WgradPlan* p) {
   ShareScope share_scope(d);
-  *bias_done = false;
-  if (d->transposed) dbias = nullptr;
   int32_t rc = check_desc(d);
   if (rc) return rc;
   if ((rc = check_tensor(x, d->dtype, "x")) || (rc = check_tensor(g, d->dtype, "g"))) return rc;
   if (!dw.data || dw.dtype != TPG_F32) return fail(-13, "dw must be fp32");
-  WgradArgs a;
-  memset(&a, 0, sizeof(a));
+  memset(p, 0, sizeof(*p));
+  WgradArgs& a = p->a;
+  p->p_is_x = d->transposed;
   const tpg_tensor& P = d->transposed ? x : g;  // iteration grid operand
   const tpg_tensor& Q = d->transposed ? g : x;  // gathered operand
   const int PH = d->transposed ? d->in_h : d->out_h, PW = d->transposed ? d->in_w : d->out_w;
@@ -1211,8 +1220,8 @@ static int32_t bwd_filter_impl(const tpg_conv_desc* d, const tpg_tensor& x, cons
   const int Ca = d->transposed ? d->in_c : d->out_c, cb = d->transposed ? d->out_c : d->in_c;
   const bool comp = d->transposed ? bwd_data_composite(d, &g, nullptr) : fwd_composite(d, &x, nullptr);
   if (!comp && big_taps(d)) return fail(-4, "%dx%d kernel: only the dense NHWC GEMM form is supported", d->kh, d->kw);
-  a.P = P.data; a.p_sn = P.stride[0]; a.p_sh = P.stride[2]; a.p_sw = P.stride[3];
-  a.Q = Q.data; a.q_sn = Q.stride[0]; a.q_sh = Q.stride[2]; a.q_sw = Q.stride[3];
+  a.p_sn = P.stride[0]; a.p_sh = P.stride[2]; a.p_sw = P.stride[3];
+  a.q_sn = Q.stride[0]; a.q_sh = Q.stride[2]; a.q_sw = Q.stride[3];
   a.Ca = Ca;
   a.vec_p = vec_ok(P, d->dtype);
   a.vec_q = vec_ok(Q, d->dtype);
@@ -1235,20 +1244,15 @@ static int32_t bwd_filter_impl(const tpg_conv_desc* d, const tpg_tensor& x, cons
       }
   }
   a.npix = d->n * a.PH * a.PW;
-  a.dW = reinterpret_cast<float*>(dw.data);
   a.w_sa = dw.stride[0]; a.w_sb = dw.stride[1]; a.w_sr = dw.stride[2]; a.w_ss = dw.stride[3];
   a.div_pw.init(a.PW);
   a.div_phpw.init(a.PH * a.PW);
+  // the bias gradient rides on the halo and flat launches of a Conv2d (its pixel grid is g's)
+  p->sums_bias = !d->transposed;
   // kernel-row halo kernel (stride-1 Conv2d, bf16, 64-pixel row segments): algo 6, and the
   // default for untuned calls when it applies
   const bool rh_algo = d->algo >= 6 && d->algo <= 12;
-  if ((d->algo == 0 || rh_algo) && !comp && !d->transposed) {
-    const int rc = wgrad_rh(d, x, g, dw, dbias, (hipStream_t)stream);
-    if (rc != 1) {
-      *bias_done = rc == 0 && dbias != nullptr;
-      return rc;
-    }
-  }
+  if ((d->algo == 0 || rh_algo) && !comp && !d->transposed && plan_wgrad_rh(d, x, g, dw, p)) return 0;
   if (rh_algo) return fail(-30, "wgrad: row-halo kernel does not apply to this shape");
   // pipelined DMA kernel when both operands are 16-byte aligned channels-last rows
   if (a.vec_p && a.vec_q) {
@@ -1301,11 +1305,11 @@ static int32_t bwd_filter_impl(const tpg_conv_desc* d, const tpg_tensor& x, cons
                 (int64_t)PH * PW > kp;
       a.dpy = kp / a.PW;
       a.dpx = kp % a.PW;
-      a.dbias = dbias;
       a.bshare = deterministic() ? 1 : std::max(1, std::min((int)((ncols + bn - 1) / bn) * ngrid, 16 / a.ksplit));
-      const int32_t r2 = hip_check(do_wgrad2(a, d->dtype, wgrad2_cfg(bm, bn), bm, bn, (hipStream_t)stream), "wgrad2");
-      *bias_done = r2 == 0 && dbias != nullptr;
-      return r2;
+      p->kernel = TPG_WGRAD_FLAT;
+      p->cfg = wgrad2_cfg(bm, bn); p->bm = bm; p->bn = bn;
+      p->tiles = cdiv(a.Ca, bm) * (int)((ncols + bn - 1) / bn) * ngrid;
+      return 0;
     }
   }
   const int cfg = (a.Ca >= 128 && a.Cb >= 128) ? 1 : 0;
@@ -1316,8 +1320,66 @@ static int32_t bwd_filter_impl(const tpg_conv_desc* d, const tpg_tensor& x, cons
   if (deterministic()) ks = 1;
   a.pix_per_split = (int)rup(cdiv(a.npix, ks), 32);
   a.ksplit = cdiv(a.npix, a.pix_per_split);
+  p->kernel = TPG_WGRAD_GENERIC;
+  p->cfg = cfg; p->bm = bm; p->bn = bn; p->tiles = tiles;
+  p->sums_bias = false;  // (the generic kernel has no bias sum)
+  return 0;
+}
+
+// The launch sequence of a plan; dbias may be null.  The flat kernel records into an open
+// launch group (do_wgrad2); the others flush it first.
+static int32_t run_wgrad(WgradPlan& p, const tpg_tensor& x, const tpg_tensor& g, const tpg_tensor& dw, float* dbias,
+                         hipStream_t stream) {
+  if (!p.sums_bias) dbias = nullptr;
+  if (p.kernel == TPG_WGRAD_ROW_HALO || p.kernel == TPG_WGRAD_IMAGE_HALO) {
+    p.rh.P = g.data; p.rh.Q = x.data;
+    p.rh.dW = reinterpret_cast<float*>(dw.data);
+    p.rh.dbias = dbias;
+    TPG_GROUP_SYNC();
+    return hip_check(launch_wgrad_rh(p.rh, stream), "wgrad_rh");
+  }
+  p.a.P = p.p_is_x ? x.data : g.data;
+  p.a.Q = p.p_is_x ? g.data : x.data;
+  p.a.dW = reinterpret_cast<float*>(dw.data);
+  if (p.kernel == TPG_WGRAD_FLAT) {
+    p.a.dbias = dbias;
+    return hip_check(do_wgrad2(p.a, x.dtype, p.cfg, p.bm, p.bn, stream), "wgrad2");
+  }
   TPG_GROUP_SYNC();
-  return hip_check(launch_wgrad(a, d->dtype, cfg, (hipStream_t)stream), "wgrad");
+  return hip_check(launch_wgrad(p.a, x.dtype, p.cfg, stream), "wgrad");
+}
+
+// Weight gradient; with dbias (Conv2d only: the pixel-grid operand is g) the bias gradient is
+// summed by the same launch where the kernel supports it (*bias_done), else left to the caller.
+static int32_t bwd_filter_impl(const tpg_conv_desc* d, const tpg_tensor& x, const tpg_tensor& g, const tpg_tensor& dw,
+                               float* dbias, bool* bias_done, tpg_stream_t stream) {
+  *bias_done = false;
+  WgradPlan p;
+  int32_t rc = plan_bwd_filter(d, x, g, dw, &p);
+  if (rc) return rc;
+  rc = run_wgrad(p, x, g, dw, dbias, (hipStream_t)stream);
+  *bias_done = rc == 0 && dbias != nullptr && p.sums_bias;
+  return rc;
+}
+
+extern "C" int32_t tpg_conv2d_wgrad_plan(const tpg_conv_desc* d, tpg_tensor x, tpg_tensor g, tpg_tensor dw,
+                                         tpg_wgrad_plan* out) {
+  if (!out) return fail(-1, "null plan");
+  WgradPlan p;
+  const int32_t rc = plan_bwd_filter(d, x, g, dw, &p);
+  if (rc) return rc;
+  const bool rh = p.kernel == TPG_WGRAD_ROW_HALO || p.kernel == TPG_WGRAD_IMAGE_HALO;
+  out->kernel = p.kernel; out->cfg = p.cfg; out->tile_m = p.bm; out->tile_n = p.bn;
+  out->splits = rh ? p.rh.ksplit : p.a.ksplit;
+  out->per_split = rh ? p.rh.kt_per_split : p.a.pix_per_split;
+  out->tiles = p.tiles;
+  out->taps_per_block = p.rh.nr * p.rh.nt;
+  out->bias_share = rh ? p.rh.bshare : p.a.bshare;
+  out->flags = (p.sums_bias ? TPG_WGRAD_SUMS_BIAS : 0) | (p.a.bflat ? TPG_WGRAD_BFLAT : 0) |
+               (p.a.fastp ? TPG_WGRAD_FASTP : 0) | (p.a.fastq ? TPG_WGRAD_FASTQ : 0) |
+               (p.rh.skip ? TPG_WGRAD_SKIP : 0) |
+               (p.kernel == TPG_WGRAD_FLAT && p.a.bflat ? TPG_WGRAD_GROUPED : 0);
+  return 0;
 }
 
 extern "C" int32_t tpg_conv2d_bwd_filter(const tpg_conv_desc* d, tpg_tensor x, tpg_tensor g, tpg_tensor dw, void* ws,

@@ -38,6 +38,14 @@ class ConvDesc(ctypes.Structure):
         ("data_algo", ctypes.c_int32), ("in_act", ctypes.c_int32), ("in_slope", ctypes.c_float)]
 
 
+class WgradPlan(ctypes.Structure):  # tpg_wgrad_plan
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "kernel", "cfg", "tile_m", "tile_n", "splits", "per_split", "tiles", "taps_per_block", "bias_share", "flags")]
+
+
+WGRAD_KERNELS = ("generic", "flat", "row_halo", "image_halo")  # (TPG_WGRAD_*, by value)
+
+
 class L1Seg(ctypes.Structure):  # tpg_l1_seg
     _fields_ = [("n", ctypes.c_int32), ("c", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
                 ("a", TpgTensor), ("b", TpgTensor), ("da", TpgTensor), ("weight", ctypes.c_float)]
@@ -58,6 +66,8 @@ EXPORTS = {
                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "tpg_conv2d_bwd_filter": (ctypes.c_int32, [ctypes.POINTER(ConvDesc), TpgTensor, TpgTensor, TpgTensor,
                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "tpg_conv2d_wgrad_plan": (ctypes.c_int32, [ctypes.POINTER(ConvDesc), TpgTensor, TpgTensor, TpgTensor,
+                                               ctypes.POINTER(WgradPlan)]),
     "tpg_conv2d_bwd": (ctypes.c_int32, [ctypes.POINTER(ConvDesc), TpgTensor, TpgTensor, TpgTensor, TpgTensor,
                                         TpgTensor, TpgTensor, TpgTensor, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_size_t, ctypes.c_void_p]),

@@ -256,13 +256,11 @@ class ConvGeom:
 AUTOTUNE = {"enabled": True, "cache": {}, "trials": 0, "frozen": False}
 # (adding the library's own split for each tile, which fills whole rounds of the chip and won
 # several isolated trials, measured 36.22-36.26 vs 36.10-36.14 ms/step in round 3)
-_WG_SPLITS = (1, 2, 4, 8, 16, 32, 64)
 # between the powers of two: the 128 x 32 row-halo tile of enhance_128 (70 tiles) fills the
 # chip's 512 resident blocks best at 36 splits -- 1.381 vs 1.405 ms at 32 (tools/bench_layers.py
 # --wg-sweep, gpurun r06n); 3 / 6 / 12 for the one-round small-map grids (162 tiles x 3 = 1.9
-# rounds of 256 instead of 1.3 at 2).  False: powers of two; "small" False: without 3 / 6 / 12 (A/B)
-WG_SPLITS_EXTRA = {"enabled": True, "small": True}
-_WG_SPLITS_X = (1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 36, 48, 64)
+# rounds of 256 instead of 1.3 at 2)
+_WG_SPLITS = (1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 36, 48, 64)
 
 
 def _desc_tuple(d):
@@ -308,7 +306,6 @@ def _wgrad_key(d):
     return ("wgrad", _desc_tuple(d) + (int(d.flags & FLAG_CONCURRENT),))
 
 
-_TUNE_GRAPH = True
 _TUNE_REPS = 4
 _TUNE_STREAMS = {}
 
@@ -319,48 +316,6 @@ def _tune_stream():
     if s is None:
         s = _TUNE_STREAMS[dev] = torch.cuda.Stream(dev)
     return s
-
-
-def _time_wgrad(lib, d, x, g, scratch):
-    """GPU times (ms) of one tpg_conv2d_bwd_filter candidate.  Default: _TUNE_REPS launches
-    captured into one HIP graph, replayed twice, the second replay timed -- the GPU's time
-    alone.  (Eager event pairs around one launch also time the host's ~20 us ctypes issue of
-    the launch, comparable to a small layer's whole weight gradient, so candidates a few us
-    apart were ranked by host jitter; _TUNE_GRAPH = False restores that timing for A/B.)"""
-    if not _TUNE_GRAPH:
-        ms = []
-        for rep in range(2):
-            e0 = torch.cuda.Event(enable_timing=True)
-            e1 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-            check(lib.tpg_conv2d_bwd_filter(ctypes.byref(d), tt(x), tt(g), tt(scratch), None, 0, stream_ptr()))
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        return ms
-    # (capture_begin on a stream of our own rather than torch.cuda.graph(), whose entry runs
-    # gc.collect() + empty_cache() -- thousands of trials; thread-local capture: the tuner
-    # runs on autograd's device thread)
-    gr = torch.cuda.CUDAGraph()
-    cs = _tune_stream()
-    cs.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(cs):
-        gr.capture_begin(capture_error_mode="thread_local")
-        try:
-            for _ in range(_TUNE_REPS):
-                check(lib.tpg_conv2d_bwd_filter(ctypes.byref(d), tt(x), tt(g), tt(scratch), None, 0, stream_ptr()))
-        finally:
-            gr.capture_end()
-    gr.replay()
-    e0 = torch.cuda.Event(enable_timing=True)
-    e1 = torch.cuda.Event(enable_timing=True)
-    e0.record()
-    gr.replay()
-    e1.record()
-    e1.synchronize()
-    t = e0.elapsed_time(e1) / _TUNE_REPS
-    del gr
-    return [t]
 
 
 # Forward / input-gradient k-split autotuning (desc.data_ksplit): the planner splits the k-steps
@@ -379,7 +334,14 @@ _DATA_SPLIT_WS_CAP = 256 << 20
 
 
 def _time_launches(fn, reps=_TUNE_REPS):
-    """GPU ms per call of fn (a launch on the current stream), from a replayed HIP graph."""
+    """GPU ms per call of fn (a launch on the current stream): reps calls captured into one HIP
+    graph, replayed twice, the second replay timed -- the GPU's time alone.  (Eager event pairs
+    around one launch also time the host's ~20 us ctypes issue of the launch, comparable to a
+    small layer's whole weight gradient, so candidates a few us apart were ranked by host
+    jitter.)"""
+    # (capture_begin on a stream of our own rather than torch.cuda.graph(), whose entry runs
+    # gc.collect() + empty_cache() -- thousands of trials; thread-local capture: the tuner
+    # runs on autograd's device thread)
     gr = torch.cuda.CUDAGraph()
     cs = _tune_stream()
     cs.wait_stream(torch.cuda.current_stream())
@@ -464,20 +426,18 @@ def _tuned_wgrad(lib, d, x, g, dwv):
     best, best_ms = (0, 0), None
     torch.cuda.synchronize()
     for algo in range(1, 13):
-        for ks in (_WG_SPLITS if not WG_SPLITS_EXTRA["enabled"] else
-                   _WG_SPLITS_X if WG_SPLITS_EXTRA["small"] else tuple(k for k in _WG_SPLITS_X if k not in (3, 6, 12))):
+        for ks in _WG_SPLITS:
             if ks > nkt or (ks > 16 and (d.flags & FLAG_CONCURRENT)):
                 break
             d.algo, d.ksplit = algo, ks
-            rc = lib.tpg_conv2d_bwd_filter(ctypes.byref(d), tt(x), tt(g), tt(scratch), None, 0, stream_ptr())
+            def launch():
+                return lib.tpg_conv2d_bwd_filter(ctypes.byref(d), tt(x), tt(g), tt(scratch), None, 0, stream_ptr())
+            rc = launch()
             if rc == -30:  # algos 6..12 (row / image-halo kernel) do not cover this shape
                 break
             check(rc)
-            ms = _time_wgrad(lib, d, x, g, scratch)
+            t = _time_launches(lambda: check(launch()))
             AUTOTUNE["trials"] += 1
-            if not ms:
-                break
-            t = min(ms)
             if best_ms is None or t < best_ms:
                 best, best_ms = (algo, ks), t
     d.algo, d.ksplit = 0, 0
