@@ -30,6 +30,9 @@
  *   tpg_landmark_boxes      get_5_landmarks_pixal_position (UtilityMethods.py:148-164) + the crop
  *                           boxes of DataAndDataset.process (DataAndDataset.py:42-54)
  *   tpg_crop_normalize      PIL crop + ToTensor + x*2-1 (DataAndDataset.py:51-54,216-220,252-255)
+ *   tpg_resize_u8           Image.resize(size, Image.LANCZOS) of RGB u8 images of different sizes,
+ *                           bit for bit (DataAndDataset.py:247-251); tpg_resize_coeffs and
+ *                           tpg_resize_pack_job build its tables and job records on the host
  *
  * Conventions
  *   - Every tensor is described by tpg_tensor: a device pointer, a dtype and the element
@@ -393,6 +396,48 @@ int32_t tpg_landmark_boxes(int32_t n, int32_t npts, const float* lm, const float
 int32_t tpg_crop_normalize(int32_t n, int32_t c, int32_t in_h, int32_t in_w, const uint8_t* img,
                            const int64_t* img_stride, int32_t njobs, const tpg_tensor* outs, const int32_t* out_hw,
                            const int32_t* slots, const int32_t* boxes, int32_t box_stride, tpg_stream_t stream);
+
+/* Pillow's 8-bit LANCZOS resize of RGB (HWC, 3 interleaved bands) images, byte for byte what
+ * Image.resize((out_w, out_h), Image.LANCZOS) returns (DataAndDataset.py:247-251), for a batch of
+ * images of DIFFERENT sizes in two launches (one per pass).  Sides are 1..4096.  Integer
+ * arithmetic only on the device: per axis, out = clamp(((1 << 21) + sum_x src[xmin + x] * k[x])
+ * >> 22, 0, 255) in int32, along W first into a u8 image, then along H on that rounded image; a
+ * pass whose in == out is skipped.  The host side below does no device work and needs no GPU.
+ *
+ *   tpg_resize_ksize       taps per output sample, 2 * ceil(3 * max(in / out, 1)) + 1 (0 + message
+ *                          for a size outside 1..4096)
+ *   tpg_resize_coeffs      fill HOST bounds int32[out][2] = (xmin, n) and coeffs int32[out][ksize]
+ *                          (weights in 22 fractional bits, zero from n on): window weights
+ *                          lanczos((x + xmin - center + 0.5) * (1 / fs)) in double with libm sin,
+ *                          normalised by their sum in index order, rounded half away from zero
+ *   tpg_resize_table_ints  int32 count of one (in, out) table image, out * (2 + ksize): bounds then
+ *                          coeffs, back to back.  The caller keeps the images of the pairs it uses
+ *                          in ONE device int32 buffer and hands jobs their offsets.
+ *   tpg_resize_workspace   bytes of one job's intermediate image (H x out_w x 3, rounded up to 16;
+ *                          0 when either pass is skipped); negative on a bad size
+ *   tpg_resize_job_bytes   size of one job record (64)
+ *   tpg_resize_pack_job    write record `index` of the HOST array `jobs`; the caller uploads it.
+ *                          Record layout (little endian, 64 bytes):
+ *                            0 src pointer   8 row stride in bytes (>= W*3)
+ *                            16 / 24 offsets (in int32) of the W-axis (W -> out_w) and H-axis
+ *                                    (H -> out_h) table images in the table buffer
+ *                            32 byte offset (multiple of 16) of the intermediate image in the workspace
+ *                            40 H  44 W  48 out_h  52 out_w  (int32)   56 / 60 ksize of the W / H axis
+ *                          Offsets of a skipped pass are ignored.  bands must be 3.
+ *   tpg_resize_u8          resize njobs images into out, u8 [njobs][out_h][out_w][3].  jobs_dev,
+ *                          tables_dev, out and ws are device memory; ws holds every job's
+ *                          intermediate image at its offset and may be NULL when no job needs one.
+ *                          A record built for another (out_h, out_w) is skipped. */
+int32_t tpg_resize_ksize(int32_t in_size, int32_t out_size);
+int32_t tpg_resize_coeffs(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* coeffs);
+int64_t tpg_resize_table_ints(int32_t in_size, int32_t out_size);
+int64_t tpg_resize_workspace(int32_t h, int32_t w, int32_t out_h, int32_t out_w);
+size_t tpg_resize_job_bytes(void);
+int32_t tpg_resize_pack_job(void* jobs, int32_t index, const uint8_t* src, int32_t h, int32_t w, int32_t bands,
+                            int64_t row_stride, int32_t out_h, int32_t out_w, int64_t tab_h, int64_t tab_v,
+                            int64_t ws_off);
+int32_t tpg_resize_u8(int32_t njobs, const void* jobs_dev, const int32_t* tables_dev, int32_t out_h, int32_t out_w,
+                      uint8_t* out, void* ws, tpg_stream_t stream);
 
 /* Deterministic mode (process-wide, off by default; SURVEY.md §5 race detection): every
  * reduction runs in a fixed order — no split-K fp32 atomics in the conv forward / input

@@ -12,6 +12,10 @@
 //   tpg_conv2d_wgrad_plan (the weight gradient's kernel / tile / pixel-split choice and
 //   argument fill, on four tensor layouts per valid descriptor; the plan must be consistent),
 //   and the launch entry points with descriptors check_desc rejects (validation path only).
+// The LANCZOS resize's host side (tpg_resize.hip) is swept too: tpg_resize_ksize / _coeffs over a
+// seeded sample of input sizes in 1..4096 times the outputs {1, 32, 64, 128, 256}, into heap
+// arrays of exactly out*2 and out*ksize ints (an off-by-one in ksize writes past them), and the
+// job builder and size queries with malformed arguments.
 // Built with `make -C tp-gan_amd asan` (planner object compiled with -fsanitize=address on
 // the host side only; the kernels are the product's) and run by tests/test_capi.py.
 // Exit status: 0 clean, 1 a consistency check failed; ASan aborts on a memory error.
@@ -147,6 +151,87 @@ static void run_one(const tpg_conv_desc& d0, bool expect_valid) {
   free(d);
 }
 
+// Resize tables: every window must lie inside the axis and the table row, the weights of a row
+// must sum to 1.0 in 22 fractional bits up to the rounding of its taps, and the tail is zero.
+static long g_tables = 0;
+static void resize_table(int in, int out) {
+  const int ks = tpg_resize_ksize(in, out);
+  const double scale = (double)in / out, sup = 3.0 * (scale < 1.0 ? 1.0 : scale);
+  int want = (int)sup;
+  if (want < sup) ++want;
+  want = want * 2 + 1;
+  if (ks != want || tpg_resize_table_ints(in, out) != (int64_t)out * (2 + ks)) {
+    fprintf(stderr, "resize_ksize(%d, %d) = %d, expected %d\n", in, out, ks, want);
+    g_fail = 1;
+    return;
+  }
+  int32_t* bounds = (int32_t*)malloc(sizeof(int32_t) * 2 * out);
+  int32_t* k = (int32_t*)malloc(sizeof(int32_t) * (size_t)out * ks);
+  if (tpg_resize_coeffs(in, out, bounds, k) != 0) {
+    fprintf(stderr, "resize_coeffs(%d, %d): %s\n", in, out, tpg_last_error());
+    g_fail = 1;
+  } else {
+    for (int xx = 0; xx < out; ++xx) {
+      const int xmin = bounds[2 * xx], n = bounds[2 * xx + 1];
+      int64_t sum = 0;
+      for (int x = 0; x < ks; ++x) {
+        if (x >= n && k[(size_t)xx * ks + x] != 0) {
+          fprintf(stderr, "resize %d->%d: tail not zero\n", in, out);
+          g_fail = 1;
+        }
+        sum += k[(size_t)xx * ks + x];
+      }
+      if (xmin < 0 || n < 1 || n > ks || xmin + n > in || sum < (1 << 22) - n || sum > (1 << 22) + n) {
+        fprintf(stderr, "resize %d->%d row %d: xmin %d n %d sum %lld\n", in, out, xx, xmin, n, (long long)sum);
+        g_fail = 1;
+      }
+    }
+  }
+  free(bounds);
+  free(k);
+  ++g_tables;
+}
+
+static void resize_jobs() {
+  const size_t jb = tpg_resize_job_bytes();
+  char* jobs = (char*)malloc(jb * 2);  // records 0 and 1, nothing after them
+  const uint8_t* src = (const uint8_t*)0x10000;  // recorded, never dereferenced on the host
+  const int bad[] = {0, -1, 4097, -2147483647 - 1, 2147483647};
+  if (tpg_resize_pack_job(jobs, 0, src, 480, 640, 3, 1920, 128, 128, 0, 4224, 0) != 0 ||
+      tpg_resize_pack_job(jobs, 1, src, 4096, 4096, 3, 12288, 1, 4096, 0, 0, 16) != 0 ||
+      tpg_resize_workspace(480, 640, 128, 128) != 480 * 128 * 3 ||
+      tpg_resize_workspace(128, 640, 128, 128) != 0) {
+    fprintf(stderr, "resize job builder rejected a valid job: %s\n", tpg_last_error());
+    g_fail = 1;
+  }
+  int accepted = 0;
+  for (int v : bad) {
+    accepted += tpg_resize_pack_job(jobs, 1, src, v, 640, 3, 1920, 128, 128, 0, 0, 0) == 0;
+    accepted += tpg_resize_pack_job(jobs, 1, src, 480, v, 3, 12288, 128, 128, 0, 0, 0) == 0;
+    accepted += tpg_resize_pack_job(jobs, 1, src, 480, 640, 3, 1920, v, 128, 0, 0, 0) == 0;
+    accepted += tpg_resize_pack_job(jobs, 1, src, 480, 640, 3, 1920, 128, v, 0, 0, 0) == 0;
+    accepted += tpg_resize_pack_job(jobs, 1, src, 480, 640, v, 1920, 128, 128, 0, 0, 0) == 0;
+    accepted += tpg_resize_pack_job(jobs, 1, src, 480, 640, 3, v < 1920 ? v : 1919, 128, 128, 0, 0, 0) == 0;
+    accepted += tpg_resize_workspace(v, 640, 128, 128) >= 0;
+    accepted += tpg_resize_workspace(480, 640, 128, v) >= 0;
+    accepted += tpg_resize_ksize(v, 128) != 0;
+    accepted += tpg_resize_ksize(128, v) != 0;
+    accepted += tpg_resize_table_ints(v, v) != 0;
+    accepted += tpg_resize_coeffs(v, 128, (int32_t*)jobs, (int32_t*)jobs) == 0;
+    accepted += tpg_resize_coeffs(128, v, (int32_t*)jobs, (int32_t*)jobs) == 0;
+  }
+  accepted += tpg_resize_pack_job(jobs, -1, src, 480, 640, 3, 1920, 128, 128, 0, 0, 0) == 0;
+  accepted += tpg_resize_pack_job(jobs, 1, nullptr, 480, 640, 3, 1920, 128, 128, 0, 0, 0) == 0;
+  accepted += tpg_resize_pack_job(nullptr, 1, src, 480, 640, 3, 1920, 128, 128, 0, 0, 0) == 0;
+  accepted += tpg_resize_pack_job(jobs, 1, src, 480, 640, 3, 1920, 128, 128, -4, 0, 0) == 0;
+  accepted += tpg_resize_pack_job(jobs, 1, src, 480, 640, 3, 1920, 128, 128, 0, 0, 24) == 0;
+  accepted += tpg_resize_coeffs(64, 32, nullptr, nullptr) == 0;
+  accepted += tpg_resize_u8(1, nullptr, nullptr, 128, 128, nullptr, nullptr, nullptr) == 0;
+  accepted += tpg_resize_u8(-1, jobs, (const int32_t*)jobs, 128, 128, (uint8_t*)jobs, nullptr, nullptr) == 0;
+  if (accepted) { fprintf(stderr, "resize: %d malformed calls accepted\n", accepted); g_fail = 1; }
+  free(jobs);
+}
+
 static tpg_conv_desc conv(int n, int ci, int h, int w, int co, int k, int s, int p, int dt, bool T = false,
                           int op_pad = 0, int pm = TPG_PAD_ZERO) {
   tpg_conv_desc d;
@@ -251,7 +336,15 @@ int main(int argc, char** argv) {
     run_one(d, valid && d.kh <= 7 && d.kw <= 7 && d.out_h > 0 && d.out_w > 0 && d.in_h > 0);
   }
   (void)tpg_conv2d_workspace(nullptr, TPG_OP_FWD);
-  printf("planner_asan: %ld valid, %ld rejected descriptors, %ld pack jobs, %ld wgrad plans, %s\n", g_valid, g_rejected,
-         g_jobs, g_plans, g_fail ? "FAILED" : "ok");
+  // resize tables: the ends of the size range, the sizes around each output and a seeded sample
+  const int outs[5] = {1, 32, 64, 128, 256};
+  const int ends[] = {1, 2, 3, 4, 5, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 640, 1024, 4095, 4096};
+  for (int out : outs) {
+    for (int in : ends) resize_table(in, out);
+    for (int i = 0; i < 24; ++i) resize_table(1 + (int)(rnd() % 4096), out);
+  }
+  resize_jobs();
+  printf("planner_asan: %ld valid, %ld rejected descriptors, %ld pack jobs, %ld wgrad plans, %ld resize tables, %s\n",
+         g_valid, g_rejected, g_jobs, g_plans, g_tables, g_fail ? "FAILED" : "ok");
   return g_fail;
 }

@@ -14,6 +14,10 @@ Device path (no per-sample Python, no host synchronisation unless `check=True`):
     tpg_crop_normalize writes the image and the four patches, u8/255*2-1, in ONE launch.
   FaceBatcher.normalize(img_u8) -> the [-1, 1] image alone (TrainDataset's pre-cropped files:
     ship u8 over PCIe, 1/4 of the float32 bytes, normalise on the device).
+  FaceBatcher.resize(imgs, out_hw) -> uint8 [B, h, w, 3]: PIL's Image.resize(..., Image.LANCZOS) of
+    a batch of RGB images of different sizes, byte for byte, in two launches (tpg_resize_u8).
+  FaceBatcher.from_raw(imgs, lm68) -> the whole of TestDataset.__getitem__ for a batch of raw
+    photos (TestDataset(raw=True)): resize to 128, landmark rescale, crops, 64 / 32 images.
 
 The reference's five-point table ends with [68, 68] (UtilityMethods.py:148), past the 68
 landmarks: the mouth's right corner is NaN and math.floor raises ValueError in process(), so
@@ -151,13 +155,15 @@ class TrainDataset(Dataset):
 class TestDataset(Dataset):
     """Profile image + 68 landmarks -> 128x128 image, patches, 64/32 images in [-1, 1]
     (DataAndDataset.py:230-256).  pts_idx selects the five-point table (reference: NaN mouth
-    corner -> ValueError)."""
+    corner -> ValueError).  raw=True returns the unresized u8 HWC array and the float32 [68, 2]
+    landmarks instead, for FaceBatcher.from_raw on the device."""
 
-    def __init__(self, img_list, lm_list, pts_idx=None):
+    def __init__(self, img_list, lm_list, pts_idx=None, raw=False):
         super().__init__()
         self.img_list = img_list
         self.lm_list = lm_list
         self.pts_idx = pts_idx
+        self.raw = raw
         assert len(img_list) == len(lm_list)
 
     def __len__(self):
@@ -168,6 +174,8 @@ class TestDataset(Dataset):
         import UtilityMethods as UM
         img = Image.open(self.img_list[idx])
         lm = np.array(self.lm_list[idx].split(" "), np.float32).reshape(-1, 2)
+        if self.raw:
+            return {"img": np.asarray(img), "lm68": lm}
         saved = [list(v) for v in UM.five_pts_idx]
         if self.pts_idx is not None:
             UM.five_pts_idx[:] = [list(v) for v in self.pts_idx]
@@ -202,6 +210,8 @@ class FaceBatcher:
         self.check = check
         self._idx = (ctypes.c_int32 * 10)(*[v for r in pts_idx for v in r])
         self._wh = (ctypes.c_int32 * 8)(*[v for n in PATCH_NAMES for v in PATCH_SIZE[n]])
+        # LANCZOS tables of every (in, out) size pair seen so far, in one device int32 buffer
+        self._tab, self._tab_used, self._tab_off, self._tab_retired = None, 0, {}, []
 
     def _on_device(self, t, name):
         """The kernels take raw pointers: a tensor on another device (e.g. the CPU output of
@@ -263,4 +273,103 @@ class FaceBatcher:
         jobs = [("I128", H, W, -1)] + [(n, PATCH_SIZE[n][1], PATCH_SIZE[n][0], i) for i, n in enumerate(PATCH_NAMES)]
         out = self._crop(img_u8, jobs, boxes)
         out["boxes"] = boxes
+        return out
+
+    # ---- Image.resize(..., Image.LANCZOS) on the device (tpg_resize_u8)
+
+    def _table(self, in_size, out_size):
+        """Offset (in int32) of the (in, out) coefficient table in the batcher's device table buffer.
+        A table is written once, into a part of the buffer no launch has been told about, and the
+        host waits for that copy: kernels running on any stream never see a table change, and a
+        later call on any stream finds it complete.  A full buffer is replaced by a larger copy;
+        the old one stays allocated for the launches that still read it.  (A new size pair costs a
+        host synchronisation: use each pair once before capturing a graph.)"""
+        off = self._tab_off.get((in_size, out_size))
+        if off is not None:
+            return off
+        n = self.lib.tpg_resize_table_ints(in_size, out_size)
+        if n <= 0:
+            raise ValueError("resize: " + self.lib.tpg_last_error().decode())
+        host = np.empty(n, np.int32)
+        L.check(self.lib.tpg_resize_coeffs(in_size, out_size, host.ctypes.data, host.ctypes.data + 8 * out_size))
+        with torch.cuda.device(self.device):
+            if self._tab is None or self._tab_used + n > self._tab.numel():
+                new = torch.empty(max(1 << 18, 2 * (self._tab_used + n)), dtype=torch.int32, device=self.device)
+                if self._tab is not None:
+                    new[:self._tab_used].copy_(self._tab[:self._tab_used])
+                    self._tab_retired.append(self._tab)
+                self._tab = new
+            off = self._tab_used
+            self._tab[off:off + n].copy_(torch.from_numpy(host))
+            torch.cuda.current_stream().synchronize()
+        self._tab_used += n
+        self._tab_off[(in_size, out_size)] = off
+        return off
+
+    def _rgb_u8(self, t, name, dim):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != dim:
+            shape = "[B, H, W, 3]" if dim == 4 else "[H, W, 3]"
+            raise ValueError("%s must be a uint8 %s device tensor" % (name, shape))
+        self._on_device(t, name)
+        if t.shape[-1] != 3:
+            raise ValueError("%s must have 3 interleaved bands (RGB, HWC), got %d" % (name, t.shape[-1]))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+        if not (1 <= t.shape[-3] <= 4096 and 1 <= t.shape[-2] <= 4096):
+            raise ValueError("%s: sides must be in 1..4096, got %dx%d" % (name, t.shape[-2], t.shape[-3]))
+
+    def resize(self, imgs, out_hw=(128, 128)):
+        """PIL's Image.resize((w, h), Image.LANCZOS) of every image, byte for byte -> uint8 [B, h, w, 3].
+        imgs: a list of uint8 [H_i, W_i, 3] contiguous device tensors (any mix of sizes), or one
+        [B, H, W, 3] tensor.  Two launches on the current stream whatever the sizes are."""
+        out_h, out_w = int(out_hw[0]), int(out_hw[1])
+        if not (1 <= out_h <= 4096 and 1 <= out_w <= 4096):
+            raise ValueError("resize: output sides must be in 1..4096, got %dx%d" % (out_w, out_h))
+        if isinstance(imgs, torch.Tensor):
+            self._rgb_u8(imgs, "imgs", 4)
+            B, H, W = imgs.shape[0], imgs.shape[1], imgs.shape[2]
+            srcs = [(imgs.data_ptr() + b * H * W * 3, H, W) for b in range(B)]
+        else:
+            imgs = list(imgs)
+            for i, t in enumerate(imgs):
+                self._rgb_u8(t, "imgs[%d]" % i, 3)
+            srcs = [(t.data_ptr(), t.shape[0], t.shape[1]) for t in imgs]
+        B = len(srcs)
+        out = torch.empty(B, out_h, out_w, 3, dtype=torch.uint8, device=self.device)
+        if B == 0:
+            return out
+        jb = self.lib.tpg_resize_job_bytes()
+        jobs = (ctypes.c_uint8 * (B * jb))()
+        ws_bytes = 0
+        for i, (ptr, H, W) in enumerate(srcs):
+            tab_h = self._table(W, out_w) if W != out_w else 0
+            tab_v = self._table(H, out_h) if H != out_h else 0
+            L.check(self.lib.tpg_resize_pack_job(jobs, i, ptr, H, W, 3, W * 3, out_h, out_w, tab_h, tab_v, ws_bytes))
+            ws_bytes += self.lib.tpg_resize_workspace(H, W, out_h, out_w)
+        with torch.cuda.device(self.device):
+            if self._tab is None:  # copies only: no table is read, the launch still takes the buffer
+                self._tab = torch.empty(1 << 18, dtype=torch.int32, device=self.device)
+            jobs_dev = torch.frombuffer(jobs, dtype=torch.uint8).to(self.device)
+            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=self.device)
+            L.check(self.lib.tpg_resize_u8(B, jobs_dev.data_ptr(), self._tab.data_ptr(), out_h, out_w, out.data_ptr(),
+                                           ws.data_ptr(), L.stream_ptr()))
+        return out
+
+    def from_raw(self, imgs, lm68):
+        """TestDataset.__getitem__ (DataAndDataset.py:230-256) for a batch of raw photos, with no PIL
+        call: resize to 128x128, landmarks rescaled by float32(128 / size), crops, then 128 -> 64 ->
+        32 from the u8 results.  -> __call__'s dict plus "I64", "I32" ([-1, 1]) and "u8_128"."""
+        if not isinstance(imgs, torch.Tensor):
+            imgs = list(imgs)
+        u8 = self.resize(imgs, (128, 128))
+        if isinstance(imgs, torch.Tensor):
+            wh = np.array([[imgs.shape[2], imgs.shape[1]]] * imgs.shape[0], np.float64).reshape(-1, 2)
+        else:
+            wh = np.array([[t.shape[1], t.shape[0]] for t in imgs], np.float64).reshape(-1, 2)
+        scale = torch.from_numpy((128.0 / wh).astype(np.float32)).to(self.device)
+        out = self(u8, lm68, scale)
+        u64 = self.resize(u8, (64, 64))
+        out["I64"] = self.normalize(u64, "I64")
+        out["I32"] = self.normalize(self.resize(u64, (32, 32)), "I32")
+        out["u8_128"] = u8
         return out

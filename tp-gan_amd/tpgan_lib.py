@@ -121,6 +121,15 @@ EXPORTS = {
                                                                    ctypes.POINTER(ctypes.c_int32),
                                                                    ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p,
                                                                    ctypes.c_int32, ctypes.c_void_p]),
+    "tpg_resize_ksize": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32]),
+    "tpg_resize_coeffs": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    "tpg_resize_table_ints": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),
+    "tpg_resize_workspace": (ctypes.c_int64, [ctypes.c_int32] * 4),
+    "tpg_resize_job_bytes": (ctypes.c_size_t, []),
+    "tpg_resize_pack_job": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p] +
+                            [ctypes.c_int32] * 3 + [ctypes.c_int64] + [ctypes.c_int32] * 2 + [ctypes.c_int64] * 3),
+    "tpg_resize_u8": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                       ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "tpg_loss_workspace": (ctypes.c_size_t, []),
     "tpg_image_losses_fwd": (ctypes.c_int32, [ctypes.c_int32] * 4 + [TpgTensor, TpgTensor] + [ctypes.c_float] * 3 +
                              [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
