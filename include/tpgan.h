@@ -33,6 +33,12 @@
  *   tpg_resize_u8           Image.resize(size, Image.LANCZOS) of RGB u8 images of different sizes,
  *                           bit for bit (DataAndDataset.py:247-251); tpg_resize_coeffs and
  *                           tpg_resize_pack_job build its tables and job records on the host
+ *   tpg_denorm_u8           the generator's [-1, 1] output back to u8 HWC pixels: ToPILImage /
+ *                           torchvision.utils.save_image's rounding of (x+1)/2 (the reference has no
+ *                           inference script; its training loop would save samples that way)
+ *   tpg_image_metrics_u8    per-image squared error (PSNR) and SSIM of a u8 result against the u8
+ *                           ground truth (build-defined, no reference code: the validation pass of
+ *                           a TP-GAN training loop, as Pretrain.py:197-249 is for the landmark net)
  *
  * Conventions
  *   - Every tensor is described by tpg_tensor: a device pointer, a dtype and the element
@@ -438,6 +444,34 @@ int32_t tpg_resize_pack_job(void* jobs, int32_t index, const uint8_t* src, int32
                             int64_t ws_off);
 int32_t tpg_resize_u8(int32_t njobs, const void* jobs_dev, const int32_t* tables_dev, int32_t out_h, int32_t out_w,
                       uint8_t* out, void* ws, tpg_stream_t stream);
+
+/* Inference image path.
+ *   tpg_denorm_u8  x: logical [n, c, h, w], TPG_F32 / TPG_BF16 / TPG_F16, any element strides (the
+ *                  generator's outputs are channels-last views); out: u8 [n][h][w][c] contiguous
+ *                  (HWC, what Image.fromarray takes), c in 1..4.  Per element in float32, no FMA
+ *                  contraction: t = (float(x) + 1.0f) * 127.5f + 0.5f; out = 0 where t is NaN, else
+ *                  floor(t) clamped to [0, 255] -- torchvision.utils.save_image's rounding of
+ *                  (x+1)/2, and the exact inverse of tpg_crop_normalize's u/255*2-1 for all 256
+ *                  byte values with x held in f32, bf16 or f16.  Loads are vector loads where x's
+ *                  contiguous axis (w or c) and alignment allow; stores are dwords where out is
+ *                  4-byte aligned.
+ *   tpg_image_metrics_u8  a, b: u8 [n][h][w][c] contiguous, c in 1..4.  Per image:
+ *                  sse[n] (int64) = sum (a - b)^2, exact;
+ *                  ssim[n] (float; may be NULL, else h and w must be >= 11) = Wang et al.'s SSIM per
+ *                  channel, then averaged: window g (x) g, g[k] = exp(-(k-5)^2 / (2 * 1.5^2)) / sum,
+ *                  valid positions only ((h-10) x (w-10) per channel), C1 = 6.5025, C2 = 58.5225,
+ *                  mu = sum w x, sigma_xy = sum w x y - mu_x mu_y (likewise sigma_x^2, sigma_y^2),
+ *                  map = (2 mu_x mu_y + C1)(2 sigma_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(sigma_x^2 +
+ *                  sigma_y^2 + C2)), result = mean over windows and channels.  Moments, map and
+ *                  mean are float64 on the device; every sum runs in a fixed order (no atomics), so
+ *                  reruns are bit-identical.
+ *                  ws: device scratch, 8-byte aligned, at least tpg_image_metrics_workspace(n, h, w, c)
+ *                  bytes (negative on bad sizes). */
+int32_t tpg_denorm_u8(int32_t n, int32_t c, int32_t h, int32_t w, tpg_tensor x, uint8_t* out,
+                      tpg_stream_t stream);
+int64_t tpg_image_metrics_workspace(int32_t n, int32_t h, int32_t w, int32_t c);
+int32_t tpg_image_metrics_u8(int32_t n, int32_t h, int32_t w, int32_t c, const uint8_t* a, const uint8_t* b,
+                             int64_t* sse, float* ssim, void* ws, size_t ws_bytes, tpg_stream_t stream);
 
 /* Deterministic mode (process-wide, off by default; SURVEY.md §5 race detection): every
  * reduction runs in a fixed order — no split-K fp32 atomics in the conv forward / input

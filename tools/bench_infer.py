@@ -1,0 +1,145 @@
+"""Measure the inference path (tp-gan_amd/tpgan_infer.py) on the GPU.
+
+    python tools/bench_infer.py [--batch 32] [--iters 20] [--raw 640x480] [--out profiles/r08/infer.txt]
+
+Frontalizer in bf16 on a resident batch of synthetic raw WxH photos with synthetic landmarks:
+
+  - the whole fz(imgs, lm68) call (LANCZOS resize, crops, Generator forward, denorm_u8): faces/s
+    from HIP events around `iters` calls after 3 warm-up calls (which also pack the frozen
+    weights and autotune the shapes), and from the host clock around the same calls and a
+    synchronise;
+  - the Generator forward alone on the batch FaceBatcher.from_raw made (events), beside the wall
+    time of one bs32 training step recorded in profiles/r06/kernel_trace_final.txt (34.31 ms; the
+    trace does not tell forward kernels from backward ones, the same kernels serve both, so the
+    forward's share is this measurement over that step);
+  - tpg_denorm_u8 on the forward's own output and tpg_image_metrics_u8 on the result against a
+    second batch, each alone: events around `kiters` back-to-back launches, against the bytes
+    the kernel has to move (HBM peak 8 TB/s, MI355X_MICROARCH.md).  Both are launch-latency
+    sized at this batch; the --big line times them on 1024 faces, where the bytes dominate.
+
+Prints one JSON line per measurement; --out also writes them to a file.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "tp-gan_amd"))
+
+TRAIN_STEP_MS_R06 = 34.31  # profiles/r06/kernel_trace_final.txt: wall span per bs32 G+D step
+
+
+def events(fn, iters):
+    s = torch.cuda.current_stream()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record(s)
+    for _ in range(iters):
+        fn()
+    e1.record(s)
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters, (time.perf_counter() - t0) * 1e3 / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--kiters", type=int, default=200)
+    ap.add_argument("--raw", default="640x480", metavar="WxH")
+    ap.add_argument("--big", type=int, default=1024, help="faces of the kernels-alone line")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_infer.py needs a ROCm GPU (there is no CPU path)")
+    import D_and_G_model as DG
+    import tpgan_infer
+    import tpgan_ops
+
+    dev = torch.device("cuda", 0)
+    w, h = (int(v) for v in a.raw.lower().split("x"))
+    B = a.batch
+    rng = np.random.default_rng(0)
+    imgs = [torch.from_numpy(rng.integers(0, 256, (h, w, 3), dtype=np.uint8)).to(dev) for _ in range(B)]
+    lm = torch.from_numpy((rng.random((B, 68, 2)) * 0.5 + 0.25).astype(np.float32) * np.float32([w, h])).to(dev)
+    torch.manual_seed(0)
+    fz = tpgan_infer.Frontalizer(DG.Generator(64, 347, use_batchnorm=False), device=dev, compute_dtype=torch.bfloat16,
+                                 max_batch=B)
+    lines = []
+
+    def emit(d):
+        lines.append(json.dumps(d))
+        print(lines[-1], flush=True)
+
+    for _ in range(3):
+        out = fz(imgs, lm)
+    torch.cuda.synchronize()
+    ms, wall = events(lambda: fz(imgs, lm), a.iters)
+    emit({"op": "Frontalizer.__call__ (raw %dx%d photos -> u8 128x128x3), bf16" % (w, h), "batch": B,
+          "ms_per_batch": round(ms, 3), "ms_per_batch_host_clock": round(wall, 3),
+          "faces_per_s": round(B / (ms * 1e-3), 1)})
+
+    batch = fz._batcher().from_raw(imgs, lm)
+    z = torch.zeros(B, 64, device=dev)
+    G = fz.G
+
+    def fwd():
+        with torch.no_grad(), tpgan_ops.compute_dtype(torch.bfloat16):
+            return G(batch["I128"], batch["left_eye"], batch["right_eye"], batch["nose"], batch["mouth"], z, False)[0]
+    for _ in range(3):
+        x = fwd()
+    torch.cuda.synchronize()
+    ms, _ = events(fwd, a.iters)
+    emit({"op": "Generator.forward alone (frozen, packed-once weights), bf16", "batch": B, "ms_per_batch": round(ms, 3),
+          "faces_per_s": round(B / (ms * 1e-3), 1), "train_step_ms_bs32_r06": TRAIN_STEP_MS_R06,
+          "forward_over_train_step": round(ms * (32.0 / B) / TRAIN_STEP_MS_R06, 4),
+          "note": "profiles/r06/kernel_trace_final.txt does not separate forward from backward kernels; "
+                  "the share is this forward over that step's wall time"})
+
+    other = torch.from_numpy(rng.integers(0, 256, (B, 128, 128, 3), dtype=np.uint8)).to(dev)
+    for tag, n in (("batch", B), ("big", a.big)):
+        xs = x  # the forward's output: a channels-last view, pixel stride 8
+        if n != B:  # the same layout, more faces
+            xs = tpgan_ops.new_act(n, 3, 128, 128, x.dtype, dev)
+            xs.copy_(torch.rand(n, 3, 128, 128, device=dev) * 2 - 1)
+        u = tpgan_ops.denorm_u8(xs)
+        v = other if n == B else torch.randint(0, 256, (n, 128, 128, 3), dtype=torch.uint8, device=dev)
+        for _ in range(5):
+            tpgan_ops.denorm_u8(xs)
+            tpgan_ops.image_metrics(u, v)
+        torch.cuda.synchronize()
+        ms, _ = events(lambda: tpgan_ops.denorm_u8(xs), a.kiters)
+        nbytes = n * 128 * 128 * 3 * (xs.element_size() + 1)
+        emit({"op": "tpg_denorm_u8 (%s [N,3,128,128] channels-last view -> u8)" % str(xs.dtype).split(".")[-1],
+              "faces": n, "us_per_call": round(ms * 1e3, 2), "bytes": nbytes,
+              "GB_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1), "frac_of_8TBps": round(nbytes / (ms * 1e-3) / 8e12, 4),
+              "note": "algorithmic bytes (3 channels in, 3 bytes out); the view's pixel stride is %d elements, so "
+                      "the loads touch every cache line of the buffer" % xs.stride(3)})
+        ms, _ = events(lambda: tpgan_ops.image_metrics(u, v), a.kiters)
+        nbytes = 2 * n * 128 * 128 * 3
+        emit({"op": "tpg_image_metrics_u8 (SSE + SSIM, two launches, u8 [N,128,128,3] x 2)", "faces": n,
+              "us_per_call": round(ms * 1e3, 2), "bytes": nbytes, "GB_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1),
+              "faces_per_s": round(n / (ms * 1e-3), 1)})
+    # the validation call end to end: the same photos scored against the first run's result (split-K
+    # atomics reorder sums outside deterministic mode, so the two runs may differ in a few bytes)
+    for _ in range(2):
+        r = fz.evaluate(imgs, lm, out)
+    torch.cuda.synchronize()
+    ms, wall = events(lambda: fz.evaluate(imgs, lm, out), a.iters)
+    emit({"op": "Frontalizer.evaluate (the call above + SSE / PSNR / SSIM against u8 frontals)", "batch": B,
+          "ms_per_batch": round(ms, 3), "ms_per_batch_host_clock": round(wall, 3),
+          "faces_per_s": round(B / (ms * 1e-3), 1), "rerun_vs_first_run_min_psnr_db": float(r["psnr"].min()),
+          "rerun_vs_first_run_min_ssim": float(r["ssim"].min())})
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,213 @@
+"""Inference and validation with a trained TP-GAN generator: raw photos + 68 landmarks ->
+uint8 frontal faces, and PSNR / SSIM against the ground-truth frontal view.
+
+    fz = Frontalizer.from_checkpoint("ckpt", epoch=3)        # or Frontalizer(G)
+    u8 = fz(imgs, lm68)                                      # uint8 [B, 128, 128, 3]
+    r = fz.evaluate(imgs, lm68, frontal)                     # fake_u8, sse, psnr, ssim
+
+The data path is FaceBatcher.from_raw (Pillow-exact LANCZOS, landmark crops, [-1, 1]), the
+model is the product's Generator frozen in eval mode, the way back to pixels is
+tpgan_ops.denorm_u8 and the metrics are tpgan_ops.image_metrics: everything between the
+uploaded photos and the returned tensors stays on the device.  The frozen weights' bf16 / fp16
+images are packed once (tpgan_ops._FrozenPack) and again only after load_state_dict.
+"""
+import os
+import re
+
+import numpy as np
+import torch
+
+import D_and_G_model as DG
+import tpgan_ops
+from DataAndDataset import FaceBatcher
+
+
+def _check_state_dict(own, sd, what):
+    """Keys and shapes of sd against the model's, before anything is touched."""
+    if not isinstance(sd, dict):
+        raise ValueError("%s: not a state_dict (%s)" % (what, type(sd).__name__))
+    if set(sd) != set(own):
+        raise ValueError("%s: state_dict keys differ (missing %s, unexpected %s)" %
+                         (what, sorted(set(own) - set(sd))[:5], sorted(set(sd) - set(own))[:5]))
+    for k, v in sd.items():
+        if tuple(v.shape) != tuple(own[k].shape):
+            raise ValueError("%s: %s has shape %s, model %s" % (what, k, tuple(v.shape), tuple(own[k].shape)))
+
+
+class Frontalizer:
+    """A frozen Generator behind a photo-in, pixels-out interface.
+
+    G               a D_and_G_model.Generator.  It is moved to `device`, put in eval mode and its
+                    parameters stop requiring gradients -- unless it is bound to a trainer's
+                    FlatParams: such a model is used as it is (eval mode only for the duration of
+                    a call), and its packed weight images keep following the optimizer.
+    compute_dtype   torch.bfloat16 (default), torch.float16 or torch.float32.
+    max_batch       faces per forward pass of __call__ / frontalize_batch.
+    """
+
+    def __init__(self, G, device="cuda", compute_dtype=torch.bfloat16, max_batch=32):
+        if compute_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError("compute_dtype must be float32, bfloat16 or float16, got %s" % compute_dtype)
+        if int(max_batch) < 1:
+            raise ValueError("max_batch must be >= 1, got %s" % max_batch)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.compute_dtype = compute_dtype
+        self.max_batch = int(max_batch)
+        self.G = G
+        self.zdim = G.global_pathway.zdim
+        self.img_size = G.img_size
+        self._trainer_bound = any(self._is_trainer_flat(getattr(p, "_tpg_flat", None)) for p in G.parameters())
+        if not self._trainer_bound:
+            G.to(self.device)
+            G.eval()
+            for p in G.parameters():
+                p.requires_grad_(False)
+            self._new_packs()
+        self._fb = None
+
+    @staticmethod
+    def _is_trainer_flat(flat):
+        return flat is not None and not isinstance(flat, tpgan_ops._FrozenPack)
+
+    def _new_packs(self):
+        # a fresh holder per parameter: images are packed on first use and kept (epoch stays 0)
+        for p in self.G.parameters():
+            p._tpg_flat = tpgan_ops._FrozenPack()
+
+    @classmethod
+    def from_checkpoint(cls, path, epoch=None, zdim=64, num_classes=347, use_batchnorm=False, img_size=128, **kw):
+        """path: a .pth written by UtilityMethods.save_model (a bare state_dict), or a trainer
+        checkpoint directory holding G/model_epoch_<epoch>.pth (epoch=None: the largest integer
+        epoch there).  Loaded with weights_only=True; keys and shapes are checked before the model
+        is touched."""
+        if os.path.isdir(path):
+            gdir = os.path.join(path, "G")
+            if epoch is None:
+                found = [int(m.group(1)) for m in (re.fullmatch(r"model_epoch_(\d+)\.pth", f)
+                                                   for f in (os.listdir(gdir) if os.path.isdir(gdir) else [])) if m]
+                if not found:
+                    raise ValueError("no G/model_epoch_<epoch>.pth under %s" % path)
+                epoch = max(found)
+            path = os.path.join(gdir, "model_epoch_%s.pth" % epoch)
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        G = DG.Generator(zdim, num_classes, use_batchnorm=use_batchnorm, img_size=img_size)
+        _check_state_dict(G.state_dict(), sd, "checkpoint %s" % path)
+        G.load_state_dict(sd)
+        return cls(G, **kw)
+
+    def load_state_dict(self, sd):
+        """New weights (checked before anything changes); the packed images follow."""
+        _check_state_dict(self.G.state_dict(), sd, "load_state_dict")
+        self.G.load_state_dict(sd)  # in place: the parameters keep their storage
+        if self._trainer_bound:
+            for flat in {id(f): f for f in (getattr(p, "_tpg_flat", None) for p in self.G.parameters())
+                         if self._is_trainer_flat(f)}.values():
+                with torch.cuda.device(self.device):
+                    flat.weights_loaded()
+        else:
+            self._new_packs()
+
+    # ---- inputs
+    def _z(self, z, B):
+        if z is None:
+            return torch.zeros(B, self.zdim, dtype=torch.float32, device=self.device)
+        if isinstance(z, torch.Generator):
+            return torch.randn(B, self.zdim, generator=z, dtype=torch.float32, device=z.device).to(self.device)
+        if not isinstance(z, torch.Tensor) or tuple(z.shape) != (B, self.zdim):
+            raise ValueError("z must be None, a torch.Generator or a [%d, %d] tensor" % (B, self.zdim))
+        return z.to(self.device, torch.float32)
+
+    def _u8_images(self, imgs, name):
+        """A [B, H, W, 3] tensor or a list of [H_i, W_i, 3] arrays / tensors -> the same on the device."""
+        def one(t, what, dim):
+            t = torch.as_tensor(np.ascontiguousarray(t) if isinstance(t, np.ndarray) else t)
+            if t.dtype != torch.uint8 or t.dim() != dim or t.shape[-1] != 3:
+                raise ValueError("%s must be uint8 %s" % (what, "[B, H, W, 3]" if dim == 4 else "[H, W, 3]"))
+            return t.to(self.device).contiguous()
+        if isinstance(imgs, (torch.Tensor, np.ndarray)) and imgs.ndim == 4:
+            return one(imgs, name, 4)
+        return [one(t, "%s[%d]" % (name, i), 3) for i, t in enumerate(imgs)]
+
+    def _batcher(self):
+        if self._fb is None:
+            # landmark status is checked here for the whole batch, with the indices (check=False)
+            self._fb = FaceBatcher(self.device, dtype=torch.float32, check=False)
+        return self._fb
+
+    # ---- forward
+    def _forward_u8(self, batch, z):
+        G = self.G
+        was_training = G.training
+        G.eval()
+        try:
+            with torch.no_grad(), torch.cuda.device(self.device), tpgan_ops.compute_dtype(self.compute_dtype):
+                outs = G(batch["I128"], batch["left_eye"], batch["right_eye"], batch["nose"], batch["mouth"], z, False)
+                return tpgan_ops.denorm_u8(outs[0])
+        finally:
+            if was_training:
+                G.train()
+
+    def frontalize_batch(self, batch, z=None):
+        """A FaceBatcher dict ("I128" and the four patches, [-1, 1], any img_size) -> uint8 [B, S, S, 3]."""
+        names = ("I128", "left_eye", "right_eye", "nose", "mouth")
+        B = batch["I128"].shape[0]
+        z = self._z(z, B)
+        if B <= self.max_batch:
+            return self._forward_u8(batch, z)
+        parts = [self._forward_u8({k: batch[k][s:s + self.max_batch] for k in names}, z[s:s + self.max_batch])
+                 for s in range(0, B, self.max_batch)]
+        return torch.cat(parts)
+
+    def __call__(self, imgs, lm68, z=None):
+        """imgs: uint8 photos, a list of [H_i, W_i, 3] (any mix of sizes) or one [B, H, W, 3];
+        lm68: float32 [B, 68, 2] landmarks in each photo's own pixels -> uint8 [B, 128, 128, 3]."""
+        if self.img_size != 128:
+            raise ValueError("raw photos go through FaceBatcher.from_raw, which is 128-only; this generator "
+                             "has img_size %d (use frontalize_batch)" % self.img_size)
+        imgs = self._u8_images(imgs, "imgs")
+        B = len(imgs)
+        lm68 = torch.as_tensor(lm68)
+        if lm68.dtype != torch.float32 or lm68.dim() != 3 or lm68.shape[0] != B or lm68.shape[2] != 2:
+            raise ValueError("lm68 must be float32 [%d, npts, 2]" % B)
+        lm68 = lm68.to(self.device).contiguous()
+        z = self._z(z, B)
+        out = torch.empty(B, 128, 128, 3, dtype=torch.uint8, device=self.device)
+        if B == 0:
+            return out
+        fb = self._batcher()
+        # every face's landmarks first: nothing is returned for a batch with a bad one
+        wh = np.array([[t.shape[1], t.shape[0]] for t in imgs], np.float64).reshape(-1, 2)
+        scale = torch.from_numpy((128.0 / wh).astype(np.float32)).to(self.device)
+        status = fb.landmark_boxes(lm68, scale)[2]
+        bad = torch.nonzero(status != 0).flatten().tolist()
+        if bad:
+            raise ValueError("cannot convert float NaN to integer: a landmark point of face(s) %s is NaN or "
+                             "infinite" % bad)
+        for s in range(0, B, self.max_batch):
+            e = min(B, s + self.max_batch)
+            out[s:e] = self._forward_u8(fb.from_raw(imgs[s:e], lm68[s:e]), z[s:e])
+        return out
+
+    def evaluate(self, imgs, lm68, frontal, z=None):
+        """Frontalise and score against the ground-truth frontal view (uint8 [B, 128, 128, 3] on the
+        device, or a list of raw photos, resized like the inputs) -> {"fake_u8", "sse" int64 [B],
+        "psnr" float64 [B] (inf where sse is 0), "ssim" float32 [B]}."""
+        fake = self(imgs, lm68, z)
+        if isinstance(frontal, torch.Tensor) and frontal.dim() == 4 and tuple(frontal.shape[1:]) == (128, 128, 3):
+            if frontal.dtype != torch.uint8:
+                raise ValueError("frontal must be uint8 [B, 128, 128, 3] or a list of raw photos")
+            real = frontal.to(self.device).contiguous()
+        else:
+            real = self._batcher().resize(self._u8_images(frontal, "frontal"), (128, 128))
+        if real.shape != fake.shape:
+            raise ValueError("frontal holds %d faces, imgs %d" % (real.shape[0], fake.shape[0]))
+        sse, ssim = tpgan_ops.image_metrics(fake, real)
+        return {"fake_u8": fake, "sse": sse, "psnr": psnr_from_sse(sse, fake.shape[1:]), "ssim": ssim}
+
+
+def psnr_from_sse(sse, hwc):
+    """10 * log10(255^2 * H * W * C / sse) in float64 on sse's device (inf where sse is 0)."""
+    n = float(255 * 255) * float(hwc[0]) * float(hwc[1]) * float(hwc[2])
+    return 10.0 * torch.log10(n / sse.to(torch.float64))

@@ -130,6 +130,10 @@ EXPORTS = {
                             [ctypes.c_int32] * 3 + [ctypes.c_int64] + [ctypes.c_int32] * 2 + [ctypes.c_int64] * 3),
     "tpg_resize_u8": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
                                        ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "tpg_denorm_u8": (ctypes.c_int32, [ctypes.c_int32] * 4 + [TpgTensor, ctypes.c_void_p, ctypes.c_void_p]),
+    "tpg_image_metrics_workspace": (ctypes.c_int64, [ctypes.c_int32] * 4),
+    "tpg_image_metrics_u8": (ctypes.c_int32, [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 5 +
+                             [ctypes.c_size_t, ctypes.c_void_p]),
     "tpg_loss_workspace": (ctypes.c_size_t, []),
     "tpg_image_losses_fwd": (ctypes.c_int32, [ctypes.c_int32] * 4 + [TpgTensor, TpgTensor] + [ctypes.c_float] * 3 +
                              [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),

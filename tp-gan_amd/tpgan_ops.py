@@ -2136,3 +2136,61 @@ def ssd_decode(loc, cls, conf, nms_thr, top_k):
     check(lib.tpg_ssd_decode(B, n, C, loc.data_ptr(), cls.data_ptr(), float(conf), float(nms_thr), int(top_k),
                              keep.data_ptr(), score.data_ptr(), stream_ptr()))
     return keep, score
+
+
+# ---- inference image path (tpg_image.hip): [-1, 1] activations -> u8 HWC pixels, and the
+# validation metrics of a u8 result against the u8 ground truth.  Neither is differentiable.
+def denorm_u8(x):
+    """uint8 [N, H, W, C] (HWC, what Image.fromarray takes) of a float32 / bfloat16 / float16
+    logical-NCHW device tensor of any strides, C in 1..4: floor((x + 1) * 127.5 + 0.5) clamped to
+    [0, 255] in float32, NaN -> 0 (torchvision.utils.save_image's rounding of (x + 1) / 2; the exact
+    inverse of FaceBatcher.normalize).  Runs on the current stream of x's device."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError("denorm_u8: x must be a 4-D [N, C, H, W] tensor")
+    if not x.is_cuda:
+        raise ValueError("denorm_u8: x must be a device tensor, got a %s tensor" % x.device)
+    if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError("denorm_u8: x must be float32, bfloat16 or float16, got %s" % x.dtype)
+    n, c, h, w = x.shape
+    if not 1 <= c <= 4:
+        raise ValueError("denorm_u8: 1..4 channels, got %d" % c)
+    lib = load()
+    x = x.detach()
+    with torch.no_grad(), torch.cuda.device(x.device):
+        out = torch.empty(n, h, w, c, dtype=torch.uint8, device=x.device)
+        if out.numel():
+            check(lib.tpg_denorm_u8(n, c, h, w, tt(x), out.data_ptr(), stream_ptr()))
+    return out
+
+
+def image_metrics(a_u8, b_u8, ssim=True):
+    """(sse int64 [N], ssim float32 [N] or None) of two uint8 [N, H, W, C] device batches, C in
+    1..4: the exact integer sum of (a - b)^2 per image, and Wang et al.'s SSIM (Gaussian 11 x 11
+    window of sigma 1.5, valid positions, mean over positions and channels; needs H, W >= 11).
+    Runs on the current stream of the tensors' device; reruns are bit-identical."""
+    for name, t in (("a_u8", a_u8), ("b_u8", b_u8)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 4:
+            raise ValueError("image_metrics: %s must be a uint8 [N, H, W, C] tensor" % name)
+        if not t.is_cuda:
+            raise ValueError("image_metrics: %s must be a device tensor, got a %s tensor" % (name, t.device))
+    if a_u8.shape != b_u8.shape or a_u8.device != b_u8.device:
+        raise ValueError("image_metrics: a_u8 %s on %s and b_u8 %s on %s must match" %
+                         (tuple(a_u8.shape), a_u8.device, tuple(b_u8.shape), b_u8.device))
+    n, h, w, c = a_u8.shape
+    if not 1 <= c <= 4:
+        raise ValueError("image_metrics: 1..4 channels, got %d" % c)
+    if h < 1 or w < 1 or (ssim and (h < 11 or w < 11)):
+        raise ValueError("image_metrics: SSIM needs H and W >= 11, got %dx%d" % (h, w))
+    lib = load()
+    with torch.no_grad(), torch.cuda.device(a_u8.device):
+        a, b = a_u8.detach().contiguous(), b_u8.detach().contiguous()
+        sse = torch.empty(n, dtype=torch.int64, device=a.device)
+        sim = torch.empty(n, dtype=torch.float32, device=a.device) if ssim else None
+        if n:
+            nb = lib.tpg_image_metrics_workspace(n, h, w, c)
+            if nb < 0:
+                check(int(nb))
+            ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=a.device)
+            check(lib.tpg_image_metrics_u8(n, h, w, c, a.data_ptr(), b.data_ptr(), sse.data_ptr(),
+                                           sim.data_ptr() if ssim else None, ws.data_ptr(), ws.numel() * 8, stream_ptr()))
+    return sse, sim
