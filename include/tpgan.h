@@ -190,6 +190,52 @@ typedef struct tpg_wgrad_plan {
 int32_t tpg_conv2d_wgrad_plan(const tpg_conv_desc* d, tpg_tensor x, tpg_tensor g, tpg_tensor dw,
                               tpg_wgrad_plan* out);
 
+/* The plan tpg_conv2d_fwd (op TPG_OP_FWD: a = x, y = y), tpg_conv2d_bwd_data (TPG_OP_BWD_DATA:
+ * a = g, y = dx) or the masked input-gradient mode of tpg_conv2d_bwd (TPG_OP_BWD_DATA_MASKED:
+ * a = gy, y = dx, m = the forward's saved output, g = the buffer g is written to) runs for these
+ * tensors and a workspace of ws_bytes, under the same rules as tpg_conv2d_wgrad_plan: host
+ * arithmetic only, nothing dereferenced, launched or flushed.  x (input gradients with
+ * desc.in_act only; else ignored) is the conv's input.  The weights are taken as valid (fp32, or
+ * the packed image when desc.flags has WPACKED) and the forward as having no residual.  Returns
+ * the status the launch would give (0, -4, -20, -21, -32; -31: the call has no masked mode and
+ * tpg_conv2d_bwd takes the separate activation pass) and leaves *out alone when it is not 0. */
+enum { TPG_OP_BWD_DATA_MASKED = 3 };
+enum { TPG_DATA_GENERIC = 0, TPG_DATA_HALO = 1, TPG_DATA_POINTWISE = 2 };
+enum {
+  TPG_DATA_COMPOSITE = 1,    /* full-kernel GEMM form over flattened (y, x, c) channels */
+  TPG_DATA_DILATED = 2,      /* strided sub-pixel classes run as one zero-insertion problem */
+  TPG_DATA_REFLECT_FOLD = 4, /* gradient of the reflect-padded input into a temp, folded onto dx */
+  TPG_DATA_MASKED = 8,       /* act'(m) applied while the halo is staged; g written on the way */
+  TPG_DATA_IN_ACT = 16       /* desc.in_act applied by the epilogues (else a separate pass) */
+};
+#define TPG_DATA_MAX_PROBS 16 /* a stride-4 ConvTranspose2d has 16 sub-pixel classes */
+typedef struct tpg_data_prob {
+  int32_t kernel;             /* TPG_DATA_*: generic implicit GEMM (tpg_igemm.hip), halo (tpg_halo.hip) or
+                                 pointwise (tpg_pw.hip), after every fallback */
+  int32_t cfg;                /* the generic or halo kernel's config id */
+  int32_t th, tw, img;        /* halo plan: sub-tile and sub-tiles per block (generic: 0) */
+  int32_t bn, rows;           /* output channels and rows of a block */
+  int32_t halo_px;            /* halo pixels per LDS buffer (generic: 0) */
+  int32_t taps;
+  int32_t ksteps;             /* k-steps (halo: 64-byte channel steps per tap; generic: k-tiles) */
+  int32_t ksplit, kps;        /* splits over k-steps and steps per split */
+  int32_t paired;             /* halo: the last k-step runs two taps per MFMA */
+  int32_t pw_tile;            /* pointwise kernel: tile 1..4 (128x128, 128x64, 64x128, 64x64); else 0 */
+  uint64_t wp_off, wp_bytes;  /* weight region, in the workspace or (WPACKED) the packed image */
+  uint64_t sk_bytes;          /* fp32 split-K slices at sk_off (0: none) */
+} tpg_data_prob;
+typedef struct tpg_data_plan {
+  int32_t nprobs;
+  int32_t flags;              /* TPG_DATA_COMPOSITE | ... */
+  uint64_t ws_bytes;          /* tpg_conv2d_workspace(d, op) */
+  uint64_t packed_bytes;      /* the plan's weight regions (dense tensors: tpg_conv2d_packed_bytes(d, op)) */
+  uint64_t tmp_bytes;         /* reflect fold: temp at the start of the workspace */
+  uint64_t sk_off;            /* workspace offset of the split-K slices the problems share */
+  tpg_data_prob prob[TPG_DATA_MAX_PROBS];
+} tpg_data_plan;
+int32_t tpg_conv2d_data_plan(const tpg_conv_desc* d, int32_t op, tpg_tensor a, tpg_tensor y, tpg_tensor m,
+                             tpg_tensor g, tpg_tensor x, size_t ws_bytes, tpg_data_plan* out);
+
 /* Fused per-layer backward of tpg_conv2d_fwd's op (replaces aten convolution_backward of the
  * nn.Conv2d / nn.ConvTranspose2d built at ModificationLayer.py:101 / :186, plus the activation
  * backward of the layer's LeakyReLU / ReLU):

@@ -158,6 +158,121 @@ def test_wgrad_plans_match_recorded(lib):
     assert plan.kernel == -7 and b"row-halo kernel does not apply" in lib.tpg_last_error()
 
 
+def _data_gen():
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("make_data_plans",
+                                                  os.path.join(REPO, "tests", "golden", "make_data_plans.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    return gen, json.load(open(os.path.join(REPO, "tests", "golden", "data_plans.json")))
+
+
+def test_data_plans_match_recorded(lib):
+    """tpg_conv2d_data_plan returns, for every row of tests/golden/data_plans.json, exactly the
+    recorded status or plan: form flags, workspace layout and per problem the kernel it finally
+    runs on, config, tile, k split, weight region and split-K bytes.  The fixture was first taken
+    from the code before planning and launching were split (its launch sites dumped these fields
+    and returned), over TP-GAN's layer shapes, the GPU tests' geometries and a random walk,
+    crossed with op, dtype, tensor layout, CONCURRENT, deterministic mode, pre-packed weights,
+    dx accumulation, in_act and every forced k split / kernel.  It is regenerated
+    (tests/golden/make_data_plans.py) only by a change that means to move a plan."""
+    gen, fx = _data_gen()
+    assert tuple(fx["shape_fields"]) == gen.SHAPE_FIELDS and tuple(fx["plan_fields"]) == gen.PLAN_FIELDS
+    assert tuple(fx["prob_fields"]) == gen.PROB_FIELDS and len(fx["rows"]) > 2000
+    bad, statuses, kinds, flags = [], set(), set(), 0
+    k0, npf, nf = gen.PROB_FIELDS.index("kernel"), len(gen.PLAN_FIELDS), len(gen.PROB_FIELDS)
+    for r in fx["rows"]:
+        want = [r[-1]] if r[-1] < 0 else fx["plans"][r[-1]]
+        got = gen.query(L, lib, fx["shapes"][r[0]], *r[1:-1])
+        if got != want:
+            bad.append((fx["shapes"][r[0]], r[1:-1], "recorded", want, "got", got))
+        if r[-1] < 0:
+            statuses.add(r[-1])
+        else:
+            flags |= want[0]
+            kinds |= set(want[npf + k0::nf])
+    assert not bad, "%d of %d plans moved, first: %s" % (len(bad), len(fx["rows"]), bad[:3])
+    # the record covers every kernel kind, every form flag and every refusal
+    assert kinds == {0, 1, 2} and flags == 31 and statuses >= {-4, -20, -21, -31, -32}, (kinds, flags, statuses)
+    # a failing status leaves the caller's struct alone and sets the message
+    s = gen._t(2, 3, 6, 6, 8, 3, 1, 1)
+    d = _desc(2, 3, 6, 6, 8, 3, 1, 1)
+    d.flags = L.FLAG_WPACKED
+    plan = L.DataPlan(nprobs=-7)
+    rc = lib.tpg_conv2d_data_plan(ctypes.byref(d), L.OP_FWD, *gen.tensors(L, s, L.OP_FWD, L.TPG_BF16, 1), 1 << 20,
+                                  ctypes.byref(plan))
+    assert rc == -21 and plan.nprobs == -7 and b"need the generic one" in lib.tpg_last_error()
+
+
+def test_data_plan_branches(lib):
+    """The run-time decisions the plan took over, on the shapes the GPU tests run them with
+    (tests/test_gpu_ops.py test_unaligned_input_runs_generic_kernel, test_halo_512_rows_vs_torch):
+    unaligned rows fall back to the generic kernel, or -21 with pre-packed weights; the 512-row
+    tile has no masked mode (-31: tpg_conv2d_bwd takes the activation pass); a batch stride past
+    the pointwise kernel's 2^31-byte extent gives the halo kernel the same plan, one past the halo
+    kernel's 2^31 elements the generic kernel.  (The last two need a buffer of that extent to
+    run, so they are held here alone.)"""
+    gen, _ = _data_gen()
+
+    def kinds(shape, op, layout, flags=0):
+        got = gen.query(L, lib, shape, op, L.TPG_BF16, layout, flags, 0, 0, 0, 0, 0)
+        return got[0] if len(got) == 1 else [L.DATA_KERNELS[k] for k in got[len(gen.PLAN_FIELDS)::len(gen.PROB_FIELDS)]]
+
+    thin = gen._t(2, 3, 6, 6, 8, 3, 1, 1)
+    assert kinds(thin, L.OP_FWD, 0) == ["halo"] and kinds(thin, L.OP_FWD, 1) == ["generic"]
+    assert kinds(thin, L.OP_FWD, 1, L.FLAG_WPACKED) == -21
+    big = gen._t(16, 64, 128, 128, 64, 3, 1, 1)
+    got = gen.query(L, lib, big, L.OP_BWD_DATA, L.TPG_BF16, 0, 0, 0, 0, 0, 0, 0)
+    assert got[len(gen.PLAN_FIELDS) + gen.PROB_FIELDS.index("rows")] == 512
+    assert kinds(big, L.OP_BWD_DATA_MASKED, 0) == -31
+    assert kinds(gen._t(4, 64, 20, 20, 64, 3, 1, 1), L.OP_BWD_DATA_MASKED, 0) == ["halo"]
+    pw = gen._t(2, 32, 8, 8, 64, 1, 1, 0)
+    assert kinds(pw, L.OP_FWD, 0) == ["pointwise"] and kinds(pw, L.OP_FWD, 3) == ["halo"]
+    assert kinds(gen._t(3, 32, 8, 8, 64, 1, 1, 0), L.OP_FWD, 3) == ["generic"]
+
+
+def test_data_plans_agree_with_sizing(lib):
+    """What used to agree only because three entry points planned under the same scope: for every
+    recorded plan tpg_conv2d_workspace is the plan's workspace, and where the same call takes
+    pre-packed weights, tpg_conv2d_packed_bytes is the plan's packed bytes and
+    tpg_conv2d_pack_jobs gives one job per problem with taps, its region at the plan's offset."""
+    gen, fx = _data_gen()
+    npf, nf = len(gen.PLAN_FIELDS), len(gen.PROB_FIELDS)
+    jb = lib.tpg_pack_job_bytes()
+    host = ctypes.create_string_buffer(jb * 64)
+    w = L.TpgTensor()
+    w.data, w.dtype = 0x10000, L.TPG_F32
+    checked = 0
+    for r in fx["rows"]:
+        if r[-1] < 0:
+            continue
+        shape, (op, dtype, layout, flags, det, ks, algo, in_act, short) = fx["shapes"][r[0]], r[1:-1]
+        d = L.ConvDesc()
+        for k, v in zip(gen.SHAPE_FIELDS, shape):
+            setattr(d, k, v)
+        d.dtype, d.flags, d.data_ksplit, d.data_algo = dtype, flags, ks, algo
+        lib.tpg_set_deterministic(det)
+        try:
+            pop = L.OP_FWD if op == L.OP_FWD else L.OP_BWD_DATA
+            assert lib.tpg_conv2d_workspace(ctypes.byref(d), pop) == fx["plans"][r[-1]][1], r
+            got = gen.query(L, lib, shape, op, dtype, layout, flags | L.FLAG_WPACKED, det, ks, algo, in_act, short)
+            if len(got) == 1:
+                assert got[0] == -21, (r, got)
+                continue
+            assert lib.tpg_conv2d_packed_bytes(ctypes.byref(d), pop) == got[2], r
+            nj = lib.tpg_conv2d_pack_jobs(ctypes.byref(d), pop, w, 0x20000, host, 64)
+            probs = [got[i:i + nf] for i in range(npf, len(got), nf)]
+            offs = [p[gen.PROB_FIELDS.index("wp_off")] for p in probs if p[gen.PROB_FIELDS.index("taps")] > 0]
+            # (PackJob begins with PackArgs: W, four strides, then Wp)
+            regions = [int.from_bytes(host.raw[j * jb + 40:j * jb + 48], "little") - 0x20000 for j in range(nj)]
+            assert regions == offs, (r, regions, offs)
+            checked += 1
+        finally:
+            lib.tpg_set_deterministic(0)
+    assert checked > 1000
+
+
 def test_planner_sanitizer_sweep():
     """The planner (descriptor validation, plans, workspace and pre-pack sizing) rebuilt with
     host AddressSanitizer + UBSan and driven over TP-GAN's layer shapes, a seeded random walk of

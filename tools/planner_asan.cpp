@@ -1,6 +1,6 @@
 // Host-side AddressSanitizer sweep of the convolution planner (tpg_capi.hip).
 //
-// The planner (check_desc -> plan_fwd / plan_bwd_data / maybe_halo / plan_bwd_filter ->
+// The planner (check_desc -> plan_data / plan_probs / maybe_halo / plan_bwd_filter ->
 // workspace and pre-pack sizing) is pure host code: it runs before any launch and sizes the
 // buffers every kernel later indexes, so an out-of-range tap table, a vector overrun or a
 // wrong region size shows up here first.  This driver feeds it a deterministic sweep of
@@ -11,6 +11,9 @@
 //   tpg_conv2d_packed_bytes, tpg_conv2d_pack_jobs (host job table only), tpg_pack_prepare,
 //   tpg_conv2d_wgrad_plan (the weight gradient's kernel / tile / pixel-split choice and
 //   argument fill, on four tensor layouts per valid descriptor; the plan must be consistent),
+//   tpg_conv2d_data_plan (the forward, input-gradient and masked input-gradient plans of every
+//   valid descriptor on the same four layouts: kernel per problem, tiles, k splits, workspace
+//   regions; consistent, and never short of the workspace tpg_conv2d_workspace reports),
 //   and the launch entry points with descriptors check_desc rejects (validation path only).
 // The LANCZOS resize's host side (tpg_resize.hip) is swept too: tpg_resize_ksize / _coeffs over a
 // seeded sample of input sizes in 1..4096 times the outputs {1, 32, 64, 128, 256}, into heap
@@ -35,7 +38,7 @@ static uint32_t rnd() {
 static int pick(const int* v, int n) { return v[rnd() % n]; }
 
 static int g_fail = 0;
-static long g_valid = 0, g_rejected = 0, g_jobs = 0, g_plans = 0;
+static long g_valid = 0, g_rejected = 0, g_jobs = 0, g_plans = 0, g_dplans = 0;
 
 // channels-last activation of a never-dereferenced buffer, in the layouts of
 // tests/golden/make_wgrad_plans.py: 0 channels padded to 8, 1 as they are, 2 a view narrower
@@ -93,6 +96,72 @@ static void check_wgrad_plans(const tpg_conv_desc* d) {
   }
 }
 
+// The forward / input-gradient plans of a valid descriptor in every layout, offered the workspace
+// the size query reports: a plan that comes back must be one the launch sequence could run.
+static const char* data_plan_fault(const tpg_conv_desc* d, const tpg_data_plan* p, int op) {
+  if (p->nprobs < 1 || p->nprobs > TPG_DATA_MAX_PROBS) return "problem count out of range";
+  const bool packed = d->flags & TPG_FLAG_WPACKED;
+  uint64_t end = packed ? 0 : p->tmp_bytes, sk = 0;
+  for (int i = 0; i < p->nprobs; ++i) {
+    const tpg_data_prob& q = p->prob[i];
+    if (q.kernel < TPG_DATA_GENERIC || q.kernel > TPG_DATA_POINTWISE) return "kernel kind out of range";
+    if (q.kernel == TPG_DATA_GENERIC) {
+      if (q.cfg < 0 || q.cfg > 5 || q.bn < 1 || q.rows < 1) return "generic config out of range";
+    } else {
+      const bool c256 = q.cfg >= 0 && q.cfg < 24, c512 = q.cfg == 24 || q.cfg == 25;
+      const bool s2 = (q.cfg >= 40 && q.cfg <= 43) || q.cfg == 47;
+      if (!c256 && !c512 && !s2) return "halo config out of range";
+      if (q.rows != (c512 ? 512 : 256)) return "rows disagree with the config";
+      if (q.th < 1 || q.tw < 1 || q.img < 1 || (int64_t)q.th * q.tw * q.img > q.rows) return "tile larger than the block";
+      if (q.halo_px < q.img || q.halo_px > (c256 ? (q.cfg / 8 + 3) * 128 : 1024)) return "halo past its class";
+      if ((q.kernel == TPG_DATA_POINTWISE) != (q.pw_tile >= 1 && q.pw_tile <= 4)) return "pointwise tile disagrees";
+    }
+    if (q.taps > 0 && (q.ksplit < 1 || q.kps < 1 || (int64_t)q.ksplit * q.kps < q.ksteps ||
+                       (int64_t)(q.ksplit - 1) * q.kps >= q.ksteps))
+      return "k split does not cover the k-steps";
+    if (q.wp_off < end) return "weight regions overlap";
+    end = q.wp_off + q.wp_bytes;
+    if (q.sk_bytes > sk) sk = q.sk_bytes;
+  }
+  if (end > (packed ? p->packed_bytes : p->ws_bytes)) return "weight regions end outside their buffer";
+  if (p->sk_off < (packed ? p->tmp_bytes : end) || p->sk_off + sk > p->ws_bytes) return "split-K slices outside the workspace";
+  if (((p->flags & TPG_DATA_REFLECT_FOLD) != 0) != (p->tmp_bytes > 0)) return "reflect temp disagrees with the form";
+  if (p->flags & TPG_DATA_MASKED)
+    if (op != TPG_OP_BWD_DATA_MASKED || p->nprobs != 1 || p->prob[0].kernel != TPG_DATA_HALO || p->prob[0].taps < 2)
+      return "masked mode off a single multi-tap halo problem";
+  if (op == TPG_OP_BWD_DATA_MASKED && !(p->flags & TPG_DATA_MASKED)) return "masked op without masked mode";
+  return nullptr;
+}
+
+static void check_data_plans(const tpg_conv_desc* d0) {
+  const int ops[3] = {TPG_OP_FWD, TPG_OP_BWD_DATA, TPG_OP_BWD_DATA_MASKED};
+  for (int layout = 0; layout < 4; ++layout)
+    for (int op : ops) {
+      tpg_conv_desc* d = (tpg_conv_desc*)malloc(sizeof(tpg_conv_desc));
+      memcpy(d, d0, sizeof(*d));
+      if (op != TPG_OP_FWD && (layout & 1)) { d->in_act = TPG_ACT_LEAKY; d->in_slope = 0.2f; }
+      const tpg_tensor x = fake_act(d->in_c, d->in_h, d->in_w, d->dtype, layout);
+      const tpg_tensor y = fake_act(d->out_c, d->out_h, d->out_w, d->dtype, layout);
+      tpg_data_plan* p = (tpg_data_plan*)malloc(sizeof(tpg_data_plan));
+      const size_t ws = tpg_conv2d_workspace(d, op == TPG_OP_FWD ? TPG_OP_FWD : TPG_OP_BWD_DATA);
+      const int32_t rc = op == TPG_OP_FWD ? tpg_conv2d_data_plan(d, op, x, y, y, y, x, ws, p)
+                                          : tpg_conv2d_data_plan(d, op, y, x, y, y, x, ws, p);
+      ++g_dplans;
+      const char* why = nullptr;
+      if (rc == 0) why = data_plan_fault(d, p, op);
+      else if (rc != -4 && rc != -21 && rc != -32 && !(rc == -31 && op == TPG_OP_BWD_DATA_MASKED)) why = "unexpected status";
+      if (why) {
+        fprintf(stderr, "data plan (op %d, layout %d, rc %d): %s: n=%d c=%d->%d %dx%d->%dx%d k=%dx%d s=%d,%d T=%d dt=%d ks=%d algo=%d fl=%d: %s\n",
+                op, layout, rc, why, d->n, d->in_c, d->out_c, d->in_h, d->in_w, d->out_h, d->out_w, d->kh, d->kw,
+                d->stride_h, d->stride_w, d->transposed, d->dtype, d->data_ksplit, d->data_algo, d->flags,
+                rc ? tpg_last_error() : "");
+        g_fail = 1;
+      }
+      free(p);
+      free(d);
+    }
+}
+
 static void run_one(const tpg_conv_desc& d0, bool expect_valid) {
   // the descriptor is copied to a heap block of exactly its size so a read past it is caught
   tpg_conv_desc* d = (tpg_conv_desc*)malloc(sizeof(tpg_conv_desc));
@@ -138,6 +207,7 @@ static void run_one(const tpg_conv_desc& d0, bool expect_valid) {
     free(jobs);
   }
   if (ok) check_wgrad_plans(d);
+  if (ok) check_data_plans(d);
   if (!ok) {  // launch entry points must stop at validation (no device work happens)
     tpg_tensor z;
     memset(&z, 0, sizeof(z));
@@ -344,7 +414,7 @@ int main(int argc, char** argv) {
     for (int i = 0; i < 24; ++i) resize_table(1 + (int)(rnd() % 4096), out);
   }
   resize_jobs();
-  printf("planner_asan: %ld valid, %ld rejected descriptors, %ld pack jobs, %ld wgrad plans, %ld resize tables, %s\n",
-         g_valid, g_rejected, g_jobs, g_plans, g_tables, g_fail ? "FAILED" : "ok");
+  printf("planner_asan: %ld valid, %ld rejected descriptors, %ld pack jobs, %ld wgrad plans, %ld data plans, "
+         "%ld resize tables, %s\n", g_valid, g_rejected, g_jobs, g_plans, g_dplans, g_tables, g_fail ? "FAILED" : "ok");
   return g_fail;
 }

@@ -45,16 +45,10 @@ using namespace tpg;
 static thread_local std::string g_err;
 static int g_det = 0;  // tpg_set_deterministic
 
-// Share of the chip an op plans its grid for: 1, or 4 when desc.flags has TPG_FLAG_CONCURRENT
-// (the op runs beside other streams' work, e.g. the four local pathways: fewer K / pixel
-// splits, since the other streams fill the CUs a split would).  Set per entry point.
-static thread_local int g_share = 1;
 // small-map convs with several taps on the pointwise kernel (tpg_pw.hip; 0: the halo kernel, A/B)
 #ifndef TPG_PW_TAPS
 #define TPG_PW_TAPS 1
 #endif
-// forced k-step split of the forward / input-gradient launches (desc.data_ksplit; 0 = planner)
-static thread_local int g_data_ks = 0;
 // paired last k-step in the halo kernel (HaloArgs.half); TPG_HALO_PAIR=0 (read once at load, so
 // every packed image and plan of the process agree) turns it off for same-box A/B runs
 static const int g_halo_pair = [] {
@@ -67,20 +61,27 @@ static const int g_rh_skip = [] {
   const char* e = getenv("TPG_RH_SKIP");
   return (e && e[0] == '0') ? 0 : 1;
 }();
-// kernel of the small-map multi-tap forward / input-gradient plans (desc.data_algo; 0 = rule)
-static thread_local int g_data_algo = 0;
-struct ShareScope {
-  int prev, prev_ks, prev_algo;
-  explicit ShareScope(const tpg_conv_desc* d) : prev(g_share), prev_ks(g_data_ks), prev_algo(g_data_algo) {
-    g_data_ks = (d && d->data_ksplit > 0) ? d->data_ksplit : 0;
-    g_data_algo = (d && (d->data_algo == 1 || d->data_algo == 2)) ? d->data_algo : 0;
-    // (1/2 .. 1/8 measured within run-to-run spread, profiles/r02c/share)
-    g_share = (d && (d->flags & TPG_FLAG_CONCURRENT)) ? 4 : 1;
-  }
-  ~ShareScope() { g_share = prev; g_data_ks = prev_ks; g_data_algo = prev_algo; }
-};
 
 int tpg::deterministic() { return __atomic_load_n(&g_det, __ATOMIC_RELAXED); }
+
+// Everything a plan depends on besides the geometry and the tensors' layout, read once per
+// entry point: the planners below take it as an argument and read no global.
+struct PlanCtx {
+  int share;  // share of the chip the op plans its grid for: 1, or 4 with TPG_FLAG_CONCURRENT (the
+              // op runs beside other streams' work, e.g. the four local pathways: fewer K / pixel
+              // splits, since the other streams fill the CUs a split would; 1/2 .. 1/8 measured
+              // within run-to-run spread, profiles/r02c/share)
+  int ks;     // forced k-step split of the forward / input-gradient launches (desc.data_ksplit; 0 = planner)
+  int algo;   // kernel of the small-map multi-tap forward / input-gradient plans (desc.data_algo; 0 = rule)
+  bool det;   // tpg_set_deterministic
+  bool pair;  // paired last k-step in the halo kernel (g_halo_pair)
+  bool skip;  // wgrad_rh skips all-padding blocks (g_rh_skip)
+};
+static PlanCtx plan_ctx(const tpg_conv_desc* d) {
+  return {(d->flags & TPG_FLAG_CONCURRENT) ? 4 : 1, d->data_ksplit > 0 ? d->data_ksplit : 0,
+          (d->data_algo == 1 || d->data_algo == 2) ? d->data_algo : 0, deterministic() != 0, g_halo_pair != 0,
+          g_rh_skip != 0};
+}
 
 static int32_t fail(int32_t code, const char* fmt, ...) {
   char buf[512];
@@ -215,18 +216,12 @@ static GLaunch& grec(int kind, hipStream_t s, int dtype) {
   return L;
 }
 
+// (the plan settled which of the two kernels takes h: plan_data clears h.pw where the pointwise
+// kernel would refuse)
 static int do_halo(const HaloArgs& h, int dtype, int cfg, hipStream_t s, bool mask) {
-  if (h.pw > 0 && !mask) {  // (not a launch-group kernel: the recorded launches go first)
+  if (h.pw > 0) {  // (not a launch-group kernel: the recorded launches go first)
     const int rc = group_flush();
-    if (rc) return rc;
-    const int e = launch_pw(h, dtype, s);
-    if (e != -1) return e;
-    // the pointwise kernel refused the plan (its 32-bit byte-extent / stride conditions are
-    // stricter than the planner's element-count checks): the halo kernel of the same plan and
-    // packed weight image takes it
-    HaloArgs h2 = h;
-    h2.pw = 0;
-    return launch_halo(h2, dtype, cfg, s, false);
+    return rc ? rc : launch_pw(h, dtype, s);
   }
   if (!g_grp.active) return launch_halo(h, dtype, cfg, s, mask);
   GLaunch& L = grec(1, s, dtype);
@@ -297,15 +292,24 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int pmod(int a, int m) { return ((a % m) + m) % m; }
 
 // ------------------------------------------------------------------ problem plans --
+// (the argument blocks' data pointers, strides and vector flags stay zero in a plan: run_data
+// fills copies)
 struct Prob {
   IgemmArgs a;
   PackArgs pk;
   int cfg = 0;
   size_t wp_bytes = 0, sk_bytes = 0;
-  bool halo = false;          // run on the halo-tiled direct-conv kernel
+  bool halo = false;          // run on the halo-tiled direct-conv kernel (h.pw > 0: the pointwise one)
   HaloArgs h;
-  int hcfg = -1;
-  size_t g_wp = 0, g_sk = 0;  // generic-kernel sizes, kept for the run-time fallback
+  int hcfg = -1, hbm = 0;     // halo config id and rows per block
+  size_t g_wp = 0, g_sk = 0;  // generic-kernel sizes: tensors the halo kernel cannot read fall back to it
+  size_t wp_off = 0;          // weight region [wp_off, wp_off + region()) of the workspace / packed image
+  size_t region() const { return std::max(wp_bytes, g_wp); }
+  Prob() {
+    memset(&a, 0, sizeof(a));
+    memset(&pk, 0, sizeof(pk));
+    memset(&h, 0, sizeof(h));
+  }
 };
 
 static int choose_cfg(int nout) {
@@ -319,7 +323,7 @@ static int choose_cfg(int nout) {
 }
 
 // fill unit / tile / split-K bookkeeping once geometry, C, Nout and taps are known
-static void finish(Prob& P, int dtype, int M) {
+static void finish(Prob& P, const PlanCtx& cx, int dtype, int M) {
   IgemmArgs& a = P.a;
   const int upk = half16(dtype) ? 4 : 2;
   a.upt = cdiv(std::max(a.C, 1), 16);
@@ -333,9 +337,9 @@ static void finish(Prob& P, int dtype, int M) {
   const int blocks = cdiv(M, bm) * (npad / bn);
   a.ksplit = 1;
   a.kt_per_split = std::max(nkt, 1);
-  if (!deterministic() && (g_data_ks > 0 || (blocks < 480 / g_share && nkt >= 8))) {
-    int ks = g_data_ks > 0 ? std::min(g_data_ks, std::max(nkt, 1))  // (an autotuner's pick)
-                           : std::min(cdiv(960 / g_share, blocks), nkt / 4);
+  if (!cx.det && (cx.ks > 0 || (blocks < 480 / cx.share && nkt >= 8))) {
+    int ks = cx.ks > 0 ? std::min(cx.ks, std::max(nkt, 1))  // (an autotuner's pick)
+                      : std::min(cdiv(960 / cx.share, blocks), nkt / 4);
     if (ks > 1) {
       a.kt_per_split = cdiv(nkt, ks);
       a.ksplit = cdiv(nkt, a.kt_per_split);
@@ -357,8 +361,6 @@ static void finish(Prob& P, int dtype, int M) {
 // direct form: output grid OH x OW (one class), A pixel = o*s + (r - pad)
 static Prob direct_prob(int N, int OH, int OW, int kh, int kw, int sh, int sw, int pt, int pl) {
   Prob P;
-  memset(&P.a, 0, sizeof(P.a));
-  memset(&P.pk, 0, sizeof(P.pk));
   IgemmArgs& a = P.a;
   a.JH = OH; a.JW = OW; a.oy0 = 0; a.ox0 = 0; a.osy = 1; a.osx = 1; a.ist_h = sh; a.ist_w = sw;
   a.ntaps = kh * kw;
@@ -379,8 +381,6 @@ static std::vector<Prob> subpixel_probs(int OH, int OW, int kh, int kw, int sh, 
     for (int px = 0; px < sw; ++px) {
       if (py >= OH || px >= OW) continue;
       Prob P;
-      memset(&P.a, 0, sizeof(P.a));
-      memset(&P.pk, 0, sizeof(P.pk));
       IgemmArgs& a = P.a;
       a.JH = cdiv(OH - py, sh); a.JW = cdiv(OW - px, sw);
       a.oy0 = py; a.ox0 = px; a.osy = sh; a.osx = sw; a.ist_h = 1; a.ist_w = 1;
@@ -417,8 +417,6 @@ static bool use_dilated(int OH, int OW, int kh, int kw, int sh, int sw, int pad_
 // four on maps where each class launch is mostly fixed cost
 static Prob dilated_prob(int OH, int OW, int kh, int kw, int s, int pt, int pl) {
   Prob P;
-  memset(&P.a, 0, sizeof(P.a));
-  memset(&P.pk, 0, sizeof(P.pk));
   IgemmArgs& a = P.a;
   a.JH = OH; a.JW = OW; a.oy0 = 0; a.ox0 = 0; a.osy = 1; a.osx = 1; a.ist_h = 1; a.ist_w = 1;
   a.dil = s;
@@ -492,7 +490,7 @@ static int32_t check_desc(const tpg_conv_desc* d) {
 // of one image (large maps) or IMG whole images per 256-row block (small maps), minimising
 // computed rows x taps plus staged halo pixels; then a split over k-steps when the grid
 // has too few blocks to fill the chip (fp32 partial slices, summed by the epilogue).
-static void maybe_halo(Prob& P, int dtype, int N) {
+static void maybe_halo(Prob& P, const PlanCtx& cx, int dtype, int N) {
   IgemmArgs& a = P.a;
   // unit-stride grids, and stride 2 in both directions (halo (2·th + k − 2) x (2·tw + k − 2))
   const int S = a.ist_h;
@@ -562,14 +560,13 @@ static void maybe_halo(Prob& P, int dtype, int N) {
   const int cfg = bm == 512 ? halo_cfg512(bn) : halo_cfg(S == 2 ? 8 : hl, bn);
   if (cfg < 0) return;
   HaloArgs& h = P.h;
-  memset(&h, 0, sizeof(h));
   const int ks_elems = half16(dtype) ? 32 : 16;
   h.A_H = a.A_H; h.A_W = a.A_W; h.C = a.C;
   h.nks = cdiv(a.C, ks_elems);
   h.ntaps = a.ntaps;
   // (16-bit: a last k-step with <= 16 live channels runs two taps per MFMA; never on the
   // pointwise kernel, which needs C % 32 == 0)
-  h.half = (half16(dtype) && g_halo_pair && a.C % 32 != 0 && a.C % 32 <= 16) ? 1 : 0;
+  h.half = (half16(dtype) && cx.pair && a.C % 32 != 0 && a.C % 32 <= 16) ? 1 : 0;
   h.dymin = dymin; h.dxmin = dxmin;
   h.TH = bth; h.TW = btw; h.IMG = bimg; h.SH = S; h.SW = S; h.dil = a.dil;
   h.HH = (bth - 1) * S + sy; h.HW = (btw - 1) * S + sx;
@@ -589,11 +586,11 @@ static void maybe_halo(Prob& P, int dtype, int N) {
   constexpr int split_below = 256, split_to = 256, split_steps = 4;  // (swept in round 2: best)
   // (deterministic mode: no k-split at all, so a sample's outputs are summed in the same
   // order whatever the batch size — the DP run then matches the 1-GPU run at its global batch)
-  if (base < split_below / g_share && !deterministic()) {
+  if (base < split_below / cx.share && !cx.det) {
     const int kps_min = cdiv(split_steps, a.ntaps);
-    ks = (int)std::min<int64_t>(cdiv(split_to / g_share, (int)base), std::max(1, h.nks / kps_min));
+    ks = (int)std::min<int64_t>(cdiv(split_to / cx.share, (int)base), std::max(1, h.nks / kps_min));
   }
-  if (g_data_ks > 0 && !deterministic()) ks = std::min(g_data_ks, h.nks);  // (an autotuner's pick)
+  if (cx.ks > 0 && !cx.det) ks = std::min(cx.ks, h.nks);  // (an autotuner's pick)
   // one tap (1x1 convs, stride 1 or 2) on whole 32-channel k-steps: the pointwise GEMM kernel,
   // whose 4-stage DMA ring hides the loads this kernel exposes every k-step when there is only
   // one tap per step; the largest of its tiles that still gives a chip's worth of blocks, and a
@@ -602,8 +599,8 @@ static void maybe_halo(Prob& P, int dtype, int N) {
   // where the halo grid is too small for the chip and would split K and the input is at most 256
   // channels deep (measured: local_20 128 ch 0.034 -> 0.021 ms, ResNet-50 l2 3x3 0.028 -> 0.018;
   // 512 / 768-channel maps slower, they keep the halo); desc.data_algo overrides (autotuner)
-  const bool small_map = a.ntaps > 1 && (g_data_algo == 2 || (g_data_algo == 0 && TPG_PW_TAPS &&
-                                                              base < split_below / g_share && a.C <= 256));
+  const bool small_map = a.ntaps > 1 && (cx.algo == 2 || (cx.algo == 0 && TPG_PW_TAPS &&
+                                                              base < split_below / cx.share && a.C <= 256));
   h.pw = 0;
   if ((a.ntaps == 1 || small_map) && a.dil <= 1 && half16(dtype) && a.C % 32 == 0 && bn % 64 == 0 && bn <= 192) {
     const int64_t M = (int64_t)N * JH * JW;
@@ -612,16 +609,17 @@ static void maybe_halo(Prob& P, int dtype, int N) {
       if (pw_tile_bn(c) > bn || bn % pw_tile_bn(c)) continue;
       const int64_t blocks = cdiv(M, pw_tile_bm(c)) * (int64_t)cdiv(a.Nout, pw_tile_bn(c));
       if (blocks > bb) { h.pw = c; bb = blocks; }
-      if (blocks >= 240 / g_share) { h.pw = c; bb = blocks; break; }
+      if (blocks >= 240 / cx.share) { h.pw = c; bb = blocks; break; }
     }
     ks = 1;
-    if (bb < 128 / g_share && !deterministic()) ks = (int)std::min<int64_t>(cdiv(256 / g_share, (int)bb), h.nks / 8);
-    if (g_data_ks > 0 && !deterministic()) ks = std::min(g_data_ks, h.nks);
+    if (bb < 128 / cx.share && !cx.det) ks = (int)std::min<int64_t>(cdiv(256 / cx.share, (int)bb), h.nks / 8);
+    if (cx.ks > 0 && !cx.det) ks = std::min(cx.ks, h.nks);
   }
   h.kps = cdiv(h.nks, std::max(ks, 1));
   h.ksplit = cdiv(h.nks, h.kps);
   P.halo = true;
   P.hcfg = cfg;
+  P.hbm = bm;
   P.g_wp = P.wp_bytes;
   P.g_sk = P.sk_bytes;
   P.wp_bytes = (size_t)rup((int64_t)halo_wp_bytes(h.nks, h.ntaps, bn, h.ntiles, h.half), 256);
@@ -630,147 +628,14 @@ static void maybe_halo(Prob& P, int dtype, int N) {
   P.sk_bytes = h.ksplit > 1 ? (size_t)rup((int64_t)h.ksplit * a.M * a.Nout * 4, 256) : 0;
 }
 
-// ---- forward plans
-static std::vector<Prob> plan_fwd(const tpg_conv_desc* d, bool composite) {
-  std::vector<Prob> v;
-  if (!d->transposed) {
-    if (composite) {
-      Prob P = direct_prob(d->n, 1, 1, 1, 1, 1, 1, 0, 0);
-      P.a.C = d->kh * d->kw * d->in_c;
-      P.a.A_H = 1; P.a.A_W = 1;
-      P.pk.cmode = 2; P.pk.nmode = 0; P.pk.comp_kw = d->kw; P.pk.comp_c = d->in_c;
-      P.a.Nout = d->out_c;
-      finish(P, d->dtype, d->n);
-      v.push_back(P);
-    } else {
-      Prob P = direct_prob(d->n, d->out_h, d->out_w, d->kh, d->kw, d->stride_h, d->stride_w, d->pad_t, d->pad_l);
-      P.a.C = d->in_c; P.a.A_H = d->in_h; P.a.A_W = d->in_w; P.a.Nout = d->out_c;
-      P.a.pad_mode = d->pad_mode;
-      P.pk.nmode = 0; P.pk.cmode = 1;
-      finish(P, d->dtype, d->n * d->out_h * d->out_w);
-      maybe_halo(P, d->dtype, d->n);
-      v.push_back(P);
-    }
-  } else {
-    if (composite) {
-      Prob P = direct_prob(d->n, 1, 1, 1, 1, 1, 1, 0, 0);
-      P.a.C = d->in_c; P.a.A_H = 1; P.a.A_W = 1;
-      P.a.Nout = d->kh * d->kw * d->out_c;
-      P.pk.nmode = 2; P.pk.cmode = 0; P.pk.comp_kw = d->kw; P.pk.comp_c = d->out_c;
-      finish(P, d->dtype, d->n);
-      v.push_back(P);
-    } else {
-      if (use_dilated(d->out_h, d->out_w, d->kh, d->kw, d->stride_h, d->stride_w, d->pad_mode)) {
-        Prob P = dilated_prob(d->out_h, d->out_w, d->kh, d->kw, d->stride_h, d->pad_t, d->pad_l);
-        P.a.C = d->in_c; P.a.A_H = d->in_h; P.a.A_W = d->in_w; P.a.Nout = d->out_c;
-        P.pk.nmode = 1; P.pk.cmode = 0;
-        finish(P, d->dtype, d->n * P.a.JH * P.a.JW);
-        maybe_halo(P, d->dtype, d->n);
-        if (P.halo) {
-          v.push_back(P);
-          return v;
-        }
-      }
-      for (Prob& P : subpixel_probs(d->out_h, d->out_w, d->kh, d->kw, d->stride_h, d->stride_w, d->pad_t, d->pad_l)) {
-        P.a.C = d->in_c; P.a.A_H = d->in_h; P.a.A_W = d->in_w; P.a.Nout = d->out_c;
-        P.pk.nmode = 1; P.pk.cmode = 0;
-        finish(P, d->dtype, d->n * P.a.JH * P.a.JW);
-        maybe_halo(P, d->dtype, d->n);
-        v.push_back(P);
-      }
-    }
-  }
-  return v;
-}
-
-static bool fwd_composite(const tpg_conv_desc* d, const tpg_tensor* x, const tpg_tensor* y) {
-  if (!d->transposed) {
-    if (d->in_h != d->kh || d->in_w != d->kw || d->out_h != 1 || d->out_w != 1) return false;
-    if (d->pad_t || d->pad_b || d->pad_l || d->pad_r || d->pad_mode) return false;
-    if (d->kh == 1 && d->kw == 1) return false;
-    return !x || dense_nhwc(*x, d->in_c, d->in_h, d->in_w);
-  }
-  if (d->in_h != 1 || d->in_w != 1 || d->out_h != d->kh || d->out_w != d->kw) return false;
-  if (d->pad_t || d->pad_b || d->pad_l || d->pad_r) return false;
-  if (d->kh == 1 && d->kw == 1) return false;
-  return !y || dense_nhwc(*y, d->out_c, d->out_h, d->out_w);
-}
-
-// ---- input-gradient plans (geometry of the op's forward; for reflect, the padded input)
-static std::vector<Prob> plan_bwd_data(const tpg_conv_desc* d, bool composite) {
-  std::vector<Prob> v;
-  if (!d->transposed) {
-    if (composite) {  // dX[n][(y,x,ci)] = sum_co g[n][co] W[co][ci][y][x]
-      Prob P = direct_prob(d->n, 1, 1, 1, 1, 1, 1, 0, 0);
-      P.a.C = d->out_c; P.a.A_H = 1; P.a.A_W = 1;
-      P.a.Nout = d->kh * d->kw * d->in_c;
-      P.pk.nmode = 2; P.pk.cmode = 0; P.pk.comp_kw = d->kw; P.pk.comp_c = d->in_c;
-      finish(P, d->dtype, d->n);
-      v.push_back(P);
-    } else {
-      const bool refl = d->pad_mode == TPG_PAD_REFLECT;
-      const int IH = refl ? d->in_h + d->pad_t + d->pad_b : d->in_h;
-      const int IW = refl ? d->in_w + d->pad_l + d->pad_r : d->in_w;
-      const int pt = refl ? 0 : d->pad_t, pl = refl ? 0 : d->pad_l;
-      if (use_dilated(IH, IW, d->kh, d->kw, d->stride_h, d->stride_w, 0)) {
-        Prob P = dilated_prob(IH, IW, d->kh, d->kw, d->stride_h, pt, pl);
-        P.a.C = d->out_c; P.a.A_H = d->out_h; P.a.A_W = d->out_w; P.a.Nout = d->in_c;
-        P.pk.nmode = 1; P.pk.cmode = 0;
-        finish(P, d->dtype, d->n * P.a.JH * P.a.JW);
-        maybe_halo(P, d->dtype, d->n);
-        if (P.halo) {
-          v.push_back(P);
-          return v;
-        }
-      }
-      for (Prob& P : subpixel_probs(IH, IW, d->kh, d->kw, d->stride_h, d->stride_w, pt, pl)) {
-        P.a.C = d->out_c; P.a.A_H = d->out_h; P.a.A_W = d->out_w; P.a.Nout = d->in_c;
-        P.pk.nmode = 1; P.pk.cmode = 0;
-        finish(P, d->dtype, d->n * P.a.JH * P.a.JW);
-        maybe_halo(P, d->dtype, d->n);
-        v.push_back(P);
-      }
-    }
-  } else {
-    if (composite) {  // dx[n][ci] = sum_{y,x,co} g[n][(y,x,co)] W[ci][co][y][x]
-      Prob P = direct_prob(d->n, 1, 1, 1, 1, 1, 1, 0, 0);
-      P.a.C = d->kh * d->kw * d->out_c; P.a.A_H = 1; P.a.A_W = 1;
-      P.a.Nout = d->in_c;
-      P.pk.nmode = 0; P.pk.cmode = 2; P.pk.comp_kw = d->kw; P.pk.comp_c = d->out_c;
-      finish(P, d->dtype, d->n);
-      v.push_back(P);
-    } else {
-      Prob P = direct_prob(d->n, d->in_h, d->in_w, d->kh, d->kw, d->stride_h, d->stride_w, d->pad_t, d->pad_l);
-      P.a.C = d->out_c; P.a.A_H = d->out_h; P.a.A_W = d->out_w; P.a.Nout = d->in_c;
-      P.pk.nmode = 0; P.pk.cmode = 1;
-      finish(P, d->dtype, d->n * d->in_h * d->in_w);
-      maybe_halo(P, d->dtype, d->n);
-      v.push_back(P);
-    }
-  }
-  return v;
-}
-
-static bool bwd_data_composite(const tpg_conv_desc* d, const tpg_tensor* g, const tpg_tensor* dx) {
-  if (!d->transposed) {
-    if (d->in_h != d->kh || d->in_w != d->kw || d->out_h != 1 || d->out_w != 1) return false;
-    if (d->pad_t || d->pad_b || d->pad_l || d->pad_r || d->pad_mode) return false;
-    if (d->kh == 1 && d->kw == 1) return false;
-    return !dx || dense_nhwc(*dx, d->in_c, d->in_h, d->in_w);
-  }
-  if (d->in_h != 1 || d->in_w != 1 || d->out_h != d->kh || d->out_w != d->kw) return false;
-  if (d->pad_t || d->pad_b || d->pad_l || d->pad_r) return false;
-  if (d->kh == 1 && d->kw == 1) return false;
-  return !g || dense_nhwc(*g, d->out_c, d->out_h, d->out_w);
-}
-
-static size_t probs_ws(const std::vector<Prob>& v) {
-  size_t wp = 0, sk = 0;
-  for (const Prob& P : v) {
-    wp += std::max(P.wp_bytes, P.g_wp);
-    sk = std::max(sk, std::max(P.sk_bytes, P.g_sk));
-  }
-  return wp + sk;
+// ---- forward / input-gradient plans
+// The full-kernel GEMM forms' geometry with a kernel of more than one tap; `in` (x, or dx in the
+// input gradient) of a Conv2d / `out` (y, or g) of a ConvTranspose2d is the tensor whose
+// (y, x, c) flatten into composite channels and must be dense NHWC.  Null: geometry alone.
+static bool composite(const tpg_conv_desc* d, const tpg_tensor* in, const tpg_tensor* out) {
+  if (!gemm_form(d) || (d->kh == 1 && d->kw == 1)) return false;
+  if (!d->transposed) return !in || dense_nhwc(*in, d->in_c, d->in_h, d->in_w);
+  return !out || dense_nhwc(*out, d->out_c, d->out_h, d->out_w);
 }
 
 static size_t reflect_tmp_bytes(const tpg_conv_desc* d) {
@@ -779,150 +644,283 @@ static size_t reflect_tmp_bytes(const tpg_conv_desc* d) {
                          rup(d->in_c, 8) * esize(d->dtype), 256);
 }
 
+// The tensors of a forward / input-gradient call as the plan sees them: strides, dtypes and
+// pointer alignment, never the data.  A = x or the incoming gradient, Y = y or dx; M, G: the
+// saved output and the g buffer of the masked input-gradient mode; X: the conv's input when
+// desc.in_act rides the epilogues.  All null: the 16-byte aligned dense tensors the workspace
+// and pre-pack queries assume.
+struct DataLayouts {
+  const tpg_tensor *A = nullptr, *Y = nullptr, *M = nullptr, *G = nullptr, *X = nullptr;
+  bool residual = false, packed = false;
+};
+
+// One finished plan of tpg_conv2d_fwd / _bwd_data / the masked attempt of tpg_conv2d_bwd.
+struct DataPlan {
+  std::vector<Prob> v;
+  tpg_conv_desc d;
+  bool fwd = true, comp = false, refl = false, masked = false, xa = false, packed = false;
+  int bias_mod = 0;
+  size_t tmp_bytes = 0;  // reflect: the padded input's gradient, at the start of the workspace
+  size_t sk_off = 0;     // split-K slices (shared by the problems, which run one after another)
+  size_t need = 0;       // bytes of workspace the launch uses
+};
+
+// weight regions in plan order, the split-K slices behind them
+static void place_regions(DataPlan* p) {
+  size_t off = 0;
+  for (Prob& P : p->v) {
+    P.wp_off = off;
+    off += P.region();
+  }
+  p->sk_off = off;
+}
+
+// The problems of (d, op) in the given form, their weight regions and the workspace they need.
+//  operands   forward: A = x, N' = out_c over the output grid; input gradient: A = g, N' = in_c
+//             over the input grid (reflect: the padded input, folded onto dx afterwards)
+//  direct     Conv2d forward / ConvTranspose2d input gradient; else sub-pixel classes, or their
+//             zero-insertion form when it gets the halo kernel
+static void plan_probs(const PlanCtx& cx, const tpg_conv_desc* d, bool fwd, bool comp, DataPlan* p) {
+  const bool direct = fwd != (d->transposed != 0);
+  const int Ca = fwd ? d->in_c : d->out_c, Cn = fwd ? d->out_c : d->in_c;
+  p->d = *d;
+  p->fwd = fwd; p->comp = comp;
+  p->refl = !fwd && !comp && reflect_tmp_bytes(d) > 0;
+  p->bias_mod = (fwd && comp && d->transposed) ? d->out_c : 0;
+  p->v.clear();
+  // operand sizes and pack modes, then the tile / split bookkeeping and the halo routing
+  auto add = [&](Prob P, int C, int Nout, int nmode, int cmode) {
+    P.a.C = C; P.a.Nout = Nout;
+    P.a.A_H = comp ? 1 : fwd ? d->in_h : d->out_h;
+    P.a.A_W = comp ? 1 : fwd ? d->in_w : d->out_w;
+    P.pk.nmode = nmode; P.pk.cmode = cmode;
+    if (comp) { P.pk.comp_kw = d->kw; P.pk.comp_c = direct ? Ca : Cn; }
+    finish(P, cx, d->dtype, d->n * P.a.JH * P.a.JW);
+    if (!comp) maybe_halo(P, cx, d->dtype, d->n);
+    p->v.push_back(P);
+  };
+  const int GH = (fwd ? d->out_h : d->in_h) + (p->refl ? d->pad_t + d->pad_b : 0);
+  const int GW = (fwd ? d->out_w : d->in_w) + (p->refl ? d->pad_l + d->pad_r : 0);
+  const int pt = p->refl ? 0 : d->pad_t, pl = p->refl ? 0 : d->pad_l;
+  if (comp) {  // e.g. dX[n][(y,x,ci)] = sum_co g[n][co] W[co][ci][y][x]
+    Prob P = direct_prob(d->n, 1, 1, 1, 1, 1, 1, 0, 0);
+    if (direct) add(P, d->kh * d->kw * Ca, Cn, 0, 2);
+    else add(P, Ca, d->kh * d->kw * Cn, 2, 0);
+  } else if (direct) {
+    Prob P = direct_prob(d->n, GH, GW, d->kh, d->kw, d->stride_h, d->stride_w, d->pad_t, d->pad_l);
+    P.a.pad_mode = d->pad_mode;
+    add(P, Ca, Cn, 0, 1);
+  } else {
+    if (use_dilated(GH, GW, d->kh, d->kw, d->stride_h, d->stride_w, 0))
+      add(dilated_prob(GH, GW, d->kh, d->kw, d->stride_h, pt, pl), Ca, Cn, 1, 0);
+    if (p->v.empty() || !p->v[0].halo) {
+      p->v.clear();
+      for (const Prob& P : subpixel_probs(GH, GW, d->kh, d->kw, d->stride_h, d->stride_w, pt, pl)) add(P, Ca, Cn, 1, 0);
+    }
+  }
+  p->tmp_bytes = p->refl ? reflect_tmp_bytes(d) : 0;
+  size_t sk = 0;
+  for (const Prob& P : p->v) sk = std::max(sk, std::max(P.sk_bytes, P.g_sk));
+  place_regions(p);
+  p->need = p->tmp_bytes + p->sk_off + sk;
+}
+
+// (the weight regions alone: the packed image of tpg_conv2d_packed_bytes / _pack_jobs)
+static size_t packed_bytes(const DataPlan& p) { return p.sk_off; }
+
+// Workspace bytes of (d, op) whatever the tensors' layout: the larger of the two forms.
+static size_t data_workspace(const PlanCtx& cx, const tpg_conv_desc* d, bool fwd) {
+  DataPlan p;
+  size_t a = 0;
+  if (!big_taps(d)) {
+    plan_probs(cx, d, fwd, false, &p);
+    a = p.need;
+  }
+  if (composite(d, nullptr, nullptr)) {
+    plan_probs(cx, d, fwd, true, &p);
+    a = std::max(a, p.need);
+  }
+  return a + 256;
+}
+
 extern "C" size_t tpg_conv2d_workspace(const tpg_conv_desc* d, int32_t op) {
-  ShareScope share_scope(d);
   if (check_desc(d)) return 0;
-  if (op == TPG_OP_FWD) {
-    size_t a = big_taps(d) ? 0 : probs_ws(plan_fwd(d, false));
-    if (fwd_composite(d, nullptr, nullptr)) a = std::max(a, probs_ws(plan_fwd(d, true)));
-    return a + 256;
-  }
-  if (op == TPG_OP_BWD_DATA) {
-    size_t a = big_taps(d) ? 0 : probs_ws(plan_bwd_data(d, false)) + reflect_tmp_bytes(d);
-    if (bwd_data_composite(d, nullptr, nullptr)) a = std::max(a, probs_ws(plan_bwd_data(d, true)));
-    return a + 256;
-  }
+  if (op == TPG_OP_FWD || op == TPG_OP_BWD_DATA) return data_workspace(plan_ctx(d), d, op == TPG_OP_FWD);
   return 256;  // bwd_filter accumulates straight into dw
 }
 
-// run a list of problems: pack -> [zero split-K] -> igemm -> [finalize]
-// Masked input-gradient mode of the halo kernel (tpg_conv2d_bwd): A = gy, M = the saved
-// output y, G = where g = gy * act'(y) goes (M's strides).
-struct HaloMask {
-  tpg_tensor M, G;
-  int act;
-  float slope;
-};
+static int64_t extent(const HaloArgs& h, const tpg_tensor& t) {
+  return (int64_t)(h.N - 1) * std::abs(t.stride[0]) + (int64_t)(h.A_H - 1) * std::abs(t.stride[2]) +
+         (int64_t)(h.A_W - 1) * std::abs(t.stride[3]) + h.C + 64;
+}
 
-// desc.in_act: the input gradient's epilogue multiplies by act'(X) (X = the conv's input x, the
-// producer's activated output, read at the output's offsets); `applied` reports whether the
-// launched plan did (every problem on the halo / pointwise kernels, X laid out like Y)
-struct HaloXA {
-  tpg_tensor X;
-  int act;
-  float slope;
-  bool applied;
-};
-
-static int32_t run_probs(std::vector<Prob>& v, int dtype, const tpg_tensor& A, const tpg_tensor& W, const float* bias,
-                         int bias_mod, const tpg_tensor& R, float res_scale, const tpg_tensor& Y, int act, float slope,
-                         char* ws, size_t ws_bytes, hipStream_t s, const char* packed = nullptr,
-                         const HaloMask* mk = nullptr, HaloXA* xa = nullptr) {
-  size_t need = probs_ws(v);
-  if (need > ws_bytes) return fail(-20, "workspace too small: %zu < %zu", ws_bytes, need);
-  const bool vA = vec_ok(A, dtype);
-  if (mk) {  // the mask mode has no generic-kernel fallback: decide before launching anything
+// The finished plan of a call, or the status the launch would give: form, the kernel every
+// problem finally runs on, masked mode, in_act in the epilogues, workspace layout.  Host
+// arithmetic on the descriptor, dtypes, strides and pointer alignment only (no HIP call, no
+// launch-group flush, no launch); run_data adds the pointers and launches.
+static int32_t plan_data(const PlanCtx& cx, const tpg_conv_desc* d, int32_t op, const DataLayouts& L, size_t ws_bytes,
+                         DataPlan* p) {
+  const bool fwd = op == TPG_OP_FWD, mask = op == TPG_OP_BWD_DATA_MASKED;
+  const int dt = d->dtype;
+  // masked mode: a stride-1 "same" Conv2d whose gy, y and g are 16-byte aligned rows, g laid out like y
+  if (mask && !(!d->transposed && d->stride_h == 1 && d->stride_w == 1 && d->pad_mode == TPG_PAD_ZERO &&
+                d->in_h == d->out_h && d->in_w == d->out_w && L.A && L.Y && L.M && L.G && L.A->dtype == dt &&
+                L.M->dtype == dt && L.Y->dtype == dt && vec_ok(*L.A, dt) && vec_ok(*L.M, dt) && vec_ok(*L.G, dt) &&
+                L.M->stride[0] == L.G->stride[0] && L.M->stride[2] == L.G->stride[2] &&
+                L.M->stride[3] == L.G->stride[3]))
+    return -31;
+  const bool comp = fwd ? composite(d, L.A, L.Y) : composite(d, L.Y, L.A);
+  if (mask && comp) return -31;
+  if (!comp && big_taps(d)) return fail(-4, "%dx%d kernel: only the dense NHWC GEMM form is supported", d->kh, d->kw);
+  if (L.packed && comp != composite(d, nullptr, nullptr))
+    return fail(-21, "pre-packed weights assume a full-kernel GEMM; these tensors are not dense NHWC");
+  plan_probs(cx, d, fwd, comp, p);
+  p->packed = L.packed;
+  if (comp && L.residual) return fail(-14, "residual not supported on a full-kernel conv");
+  // DX_ACCUM: dx's entry values ride in as the epilogue's residual (read, then overwritten by
+  // the same thread): dx = dgrad + dx
+  if (!fwd && (d->flags & TPG_FLAG_DX_ACCUM) && (comp || p->refl))
+    return fail(-32, "dx accumulation: zero-padded, non-GEMM-form geometries only");
+  if (p->need > ws_bytes) return fail(-20, "workspace too small: %zu < %zu", ws_bytes, p->need);
+  const bool vA = !L.A || vec_ok(*L.A, dt);
+  std::vector<Prob>& v = p->v;
+  if (mask) {  // the mask mode has no generic-kernel fallback
     // (the 512-row and stride-2 halo configs, ids >= 24, have no masked variant)
     if (v.size() != 1 || !v[0].halo || v[0].hcfg >= 24 || v[0].h.ntaps < 2 || !vA) return -31;
-    const int64_t ext = (int64_t)(v[0].h.N - 1) * std::abs(A.stride[0]) + (int64_t)(v[0].h.A_H - 1) * std::abs(A.stride[2]) +
-                        (int64_t)(v[0].h.A_W - 1) * std::abs(A.stride[3]) + v[0].h.C + 64;
-    const int64_t extm = (int64_t)(v[0].h.N - 1) * mk->M.stride[0] + (int64_t)(v[0].h.A_H - 1) * mk->M.stride[2] +
-                         (int64_t)(v[0].h.A_W - 1) * mk->M.stride[3] + v[0].h.C + 64;
-    if (ext >= (1ll << 31) || extm >= (1ll << 31)) return -31;
+    if (extent(v[0].h, *L.A) >= (1ll << 31) || extent(v[0].h, *L.M) >= (1ll << 31)) return -31;
+    if (!halo_accepts(v[0].h, v[0].hcfg, true)) return -31;
+    v[0].h.pw = 0;
+    p->masked = true;
   }
   for (Prob& P : v) {
-    if (!P.halo) continue;
+    if (!P.halo || !L.A) continue;
     // the halo kernel takes 16-byte aligned channels-last rows and keeps 32-bit element
     // offsets into A
-    const int64_t ext = (int64_t)(P.h.N - 1) * std::abs(A.stride[0]) + (int64_t)(P.h.A_H - 1) * std::abs(A.stride[2]) +
-                        (int64_t)(P.h.A_W - 1) * std::abs(A.stride[3]) + P.h.C + 64;
-    if (!vA || ext >= (1ll << 31)) {
-      if (packed) return fail(-21, "pre-packed weights assume the halo kernel; these tensors need the generic one");
+    if (!vA || extent(P.h, *L.A) >= (1ll << 31)) {
+      if (L.packed) return fail(-21, "pre-packed weights assume the halo kernel; these tensors need the generic one");
       P.halo = false;
       P.wp_bytes = P.g_wp;
       P.sk_bytes = P.g_sk;
+      place_regions(p);  // (its region shrinks to the generic kernel's; `need` keeps the halo plan's)
+      continue;
     }
+    // the pointwise kernel's 32-bit byte-extent / stride conditions are stricter than the element
+    // counts above: where it would refuse, the halo kernel of the same plan and packed image runs
+    P.h.a_sn = L.A->stride[0]; P.h.a_sh = L.A->stride[2]; P.h.a_sw = L.A->stride[3];
+    if (P.h.pw > 0 && !pw_accepts(P.h, dt)) P.h.pw = 0;
+    if (P.h.pw == 0 && !halo_accepts(P.h, P.hcfg, p->masked))
+      return fail(-100, "halo conv: no kernel for config %d", P.hcfg);
   }
   // the producer's act' in the epilogues: all or nothing (a partial application could not be
-  // completed by the caller's separate pass without applying it twice)
-  const void* XA = nullptr;
-  if (xa) {
-    xa->applied = false;
-    bool ok = xa->X.data && xa->X.dtype == Y.dtype && xa->X.stride[0] == Y.stride[0] && xa->X.stride[2] == Y.stride[2] &&
-              xa->X.stride[3] == Y.stride[3] && xa->X.stride[1] == 1 && vec_ok(xa->X, dtype) == vec_ok(Y, dtype);
+  // completed by the caller's separate pass without applying it twice); X laid out like Y
+  if (L.X && !p->refl) {
+    const tpg_tensor &X = *L.X, &Y = *L.Y;
+    bool ok = X.data && X.dtype == Y.dtype && X.stride[0] == Y.stride[0] && X.stride[2] == Y.stride[2] &&
+              X.stride[3] == Y.stride[3] && X.stride[1] == 1 && vec_ok(X, dt) == vec_ok(Y, dt);
     for (const Prob& P : v) ok = ok && P.halo;
-    if (ok) {
-      XA = xa->X.data;
-      xa->applied = true;
-    }
+    p->xa = ok;
   }
-  size_t off = 0;
-  std::vector<char*> wps;
-  for (Prob& P : v) {
-    wps.push_back((packed ? const_cast<char*>(packed) : ws) + off);
-    off += std::max(P.wp_bytes, P.g_wp);
+  return 0;
+}
+
+// what follows the accumulation, the same for every problem of a call
+struct Tail {
+  const float* bias;
+  tpg_tensor R, Y;
+  float res_scale;
+  int act;
+  float slope;
+  const void* XA;  // desc.in_act in the epilogues: x, read at Y's offsets
+  int xa_act;
+  float xa_slope;
+};
+
+// split-K finalize of `nslices` fp32 partial slices (1: one atomically accumulated slice)
+static EpiArgs epi_args(const IgemmArgs& a, const float* ws, int nslices, int dtype, int bias_mod, const Tail& t) {
+  EpiArgs ep;
+  memset(&ep, 0, sizeof(ep));
+  ep.ws = ws; ep.nslices = nslices; ep.slice = nslices > 1 ? (int64_t)a.M * a.Nout : 0;
+  ep.M = a.M; ep.Nout = a.Nout; ep.JH = a.JH; ep.JW = a.JW;
+  ep.Y = t.Y.data; ep.y_sn = t.Y.stride[0]; ep.y_sh = t.Y.stride[2]; ep.y_sw = t.Y.stride[3];
+  ep.oy0 = a.oy0; ep.ox0 = a.ox0; ep.osy = a.osy; ep.osx = a.osx;
+  ep.bias = t.bias; ep.bias_mod = bias_mod;
+  ep.R = t.R.data; ep.r_sn = t.R.stride[0]; ep.r_sh = t.R.stride[2]; ep.r_sw = t.R.stride[3];
+  ep.res_scale = t.res_scale; ep.act = t.act; ep.slope = t.slope; ep.dtype = dtype;
+  ep.XA = t.XA; ep.xa_act = t.xa_act; ep.xa_slope = t.xa_slope;
+  return ep;
+}
+
+// The launch sequence of a finished plan: per problem pack -> [zero split-K] -> kernel ->
+// [finalize], then the reflect fold.  A, W, Y as in DataLayouts (W: fp32 weights, or the packed
+// image of a WPACKED plan); R: the forward's residual, or dx itself under DX_ACCUM; M, G, X: the
+// tensors the plan's masked mode / in_act epilogues read.  The halo kernel and its epilogue
+// record into an open launch group; everything else flushes it first.
+static int32_t run_data(const DataPlan& p, const tpg_tensor& A, const tpg_tensor& W, const float* bias,
+                        const tpg_tensor& R, const tpg_tensor& Yc, const tpg_tensor* M, const tpg_tensor* G,
+                        const tpg_tensor* X, char* ws, hipStream_t s) {
+  const tpg_conv_desc* d = &p.d;
+  const int dtype = d->dtype;
+  tpg_tensor Y = Yc;
+  if (p.refl) {  // gradient of the padded input into a dense NHWC temp, folded onto dx below
+    const int PH = d->in_h + d->pad_t + d->pad_b, PW = d->in_w + d->pad_l + d->pad_r, Cp = (int)rup(d->in_c, 8);
+    memset(&Y, 0, sizeof(Y));
+    Y.data = ws; Y.dtype = dtype;
+    Y.stride[0] = (int64_t)PH * PW * Cp; Y.stride[1] = 1; Y.stride[2] = (int64_t)PW * Cp; Y.stride[3] = Cp;
   }
-  char* sk = ws + (packed ? 0 : off);
-  for (size_t i = 0; i < v.size(); ++i) {
-    Prob& P = v[i];
-    IgemmArgs& a = P.a;
-    PackArgs& k = P.pk;
+  const Tail t = {bias, R, Y, p.fwd ? d->res_scale : R.data ? 1.f : 0.f, p.fwd ? d->act : TPG_ACT_NONE,
+                  p.fwd ? d->slope : 0.f, p.xa ? X->data : nullptr, p.xa ? d->in_act : 0, p.xa ? d->in_slope : 0.f};
+  const bool vA = vec_ok(A, dtype);
+  char* wbase = p.packed ? reinterpret_cast<char*>(W.data) : ws + p.tmp_bytes;
+  char* sk = ws + p.tmp_bytes + (p.packed ? 0 : p.sk_off);
+  for (const Prob& P : p.v) {
+    PackArgs k = P.pk;
     k.W = reinterpret_cast<const float*>(W.data);
     k.w_sa = W.stride[0]; k.w_sb = W.stride[1]; k.w_sr = W.stride[2]; k.w_ss = W.stride[3];
-    k.Wp = wps[i];
+    k.Wp = wbase + P.wp_off;
     if (P.halo) {
-      HaloArgs& h = P.h;
-      if (h.ntaps > 0 && !packed) {
+      HaloArgs h = P.h;
+      if (h.ntaps > 0 && !p.packed) {
         TPG_GROUP_SYNC();
         int e = launch_pack_halo(k, h.nks, h.BN, h.ntiles, s);
         if (e) return hip_check(e, "pack_halo");
       }
       h.A = A.data; h.a_sn = A.stride[0]; h.a_sh = A.stride[2]; h.a_sw = A.stride[3];
       h.vec_ok = vA;
-      h.Wp = wps[i];
+      h.Wp = k.Wp;
       h.Y = Y.data; h.y_sn = Y.stride[0]; h.y_sh = Y.stride[2]; h.y_sw = Y.stride[3];
       h.bias = bias;
       h.R = R.data; h.r_sn = R.stride[0]; h.r_sh = R.stride[2]; h.r_sw = R.stride[3];
-      h.res_scale = res_scale; h.act = act; h.slope = slope;
+      h.res_scale = t.res_scale; h.act = t.act; h.slope = t.slope;
       h.ws = h.ksplit > 1 ? reinterpret_cast<float*>(sk) : nullptr;
       h.yvec = vec_ok(Y, dtype);
       h.rvec = R.data ? vec_ok(R, dtype) : 0;
-      h.wvec = a.Nout % 4 == 0;
-      if (mk) {
-        h.M = mk->M.data; h.m_sn = mk->M.stride[0]; h.m_sh = mk->M.stride[2]; h.m_sw = mk->M.stride[3];
-        h.G = mk->G.data; h.mact = mk->act; h.mslope = mk->slope;
+      h.wvec = P.a.Nout % 4 == 0;
+      if (p.masked) {
+        h.M = M->data; h.m_sn = M->stride[0]; h.m_sh = M->stride[2]; h.m_sw = M->stride[3];
+        h.G = G->data; h.mact = d->act; h.mslope = d->slope;
       }
-      h.XA = XA; h.xa_act = XA ? xa->act : 0; h.xa_slope = XA ? xa->slope : 0.f;
-      int e = do_halo(h, dtype, P.hcfg, s, mk != nullptr);
+      h.XA = t.XA; h.xa_act = t.xa_act; h.xa_slope = t.xa_slope;
+      int e = do_halo(h, dtype, P.hcfg, s, p.masked);
       if (e) return hip_check(e, "halo conv");
       if (h.ksplit > 1) {
-        EpiArgs ep;
-        memset(&ep, 0, sizeof(ep));
-        ep.ws = h.ws; ep.nslices = h.ksplit; ep.slice = (int64_t)a.M * a.Nout;
-        ep.M = a.M; ep.Nout = a.Nout; ep.JH = a.JH; ep.JW = a.JW;
-        ep.Y = Y.data; ep.y_sn = Y.stride[0]; ep.y_sh = Y.stride[2]; ep.y_sw = Y.stride[3];
-        ep.oy0 = a.oy0; ep.ox0 = a.ox0; ep.osy = a.osy; ep.osx = a.osx;
-        ep.bias = bias; ep.bias_mod = 0;
-        ep.R = R.data; ep.r_sn = R.stride[0]; ep.r_sh = R.stride[2]; ep.r_sw = R.stride[3];
-        ep.res_scale = res_scale; ep.act = act; ep.slope = slope; ep.dtype = dtype;
-        ep.XA = XA; ep.xa_act = XA ? xa->act : 0; ep.xa_slope = XA ? xa->slope : 0.f;
-        e = do_epilogue(ep, s);
+        e = do_epilogue(epi_args(P.a, h.ws, h.ksplit, dtype, 0, t), s);
         if (e) return hip_check(e, "halo epilogue");
       }
       continue;
     }
     TPG_GROUP_SYNC();
-    if (a.nunits > 0 && !packed) {
+    IgemmArgs a = P.a;
+    if (a.nunits > 0 && !p.packed) {
       int e = launch_pack(k, s);
       if (e) return hip_check(e, "pack");
     }
     a.A = A.data; a.a_sn = A.stride[0]; a.a_sh = A.stride[2]; a.a_sw = A.stride[3];
     a.vec_ok = vA;
-    a.Wp = wps[i];
+    a.Wp = k.Wp;
     a.Y = Y.data; a.y_sn = Y.stride[0]; a.y_sh = Y.stride[2]; a.y_sw = Y.stride[3];
-    a.bias = bias; a.bias_mod = bias_mod;
+    a.bias = bias; a.bias_mod = p.bias_mod;
     a.R = R.data; a.r_sn = R.stride[0]; a.r_sh = R.stride[2]; a.r_sw = R.stride[3];
-    a.res_scale = res_scale; a.act = act; a.slope = slope;
+    a.res_scale = t.res_scale; a.act = t.act; a.slope = t.slope;
     a.ws = nullptr;
     if (a.ksplit > 1) {
       a.ws = reinterpret_cast<float*>(sk);
@@ -932,19 +930,14 @@ static int32_t run_probs(std::vector<Prob>& v, int dtype, const tpg_tensor& A, c
     int e = launch_igemm(a, dtype, P.cfg, s);
     if (e) return hip_check(e, "igemm");
     if (a.ksplit > 1) {
-      EpiArgs ep;
-      memset(&ep, 0, sizeof(ep));
-      ep.ws = a.ws; ep.nslices = 1; ep.slice = 0; ep.M = a.M; ep.Nout = a.Nout; ep.JH = a.JH; ep.JW = a.JW;
-      ep.Y = a.Y; ep.y_sn = a.y_sn; ep.y_sh = a.y_sh; ep.y_sw = a.y_sw;
-      ep.oy0 = a.oy0; ep.ox0 = a.ox0; ep.osy = a.osy; ep.osx = a.osx;
-      ep.bias = bias; ep.bias_mod = bias_mod;
-      ep.R = a.R; ep.r_sn = a.r_sn; ep.r_sh = a.r_sh; ep.r_sw = a.r_sw;
-      ep.res_scale = res_scale; ep.act = act; ep.slope = slope; ep.dtype = dtype;
-      e = launch_epilogue(ep, s);
+      e = launch_epilogue(epi_args(a, a.ws, 1, dtype, p.bias_mod, t), s);
       if (e) return hip_check(e, "epilogue");
     }
   }
-  return 0;
+  if (!p.refl) return 0;
+  TPG_GROUP_SYNC();
+  return hip_check(launch_reflect_fold(d->n, d->in_c, d->in_h, d->in_w, d->pad_t, d->pad_b, d->pad_l, d->pad_r, Y, Yc, s),
+                   "reflect_fold");
 }
 
 static int32_t check_tensor(const tpg_tensor& t, int dtype, const char* name) {
@@ -955,57 +948,59 @@ static int32_t check_tensor(const tpg_tensor& t, int dtype, const char* name) {
   return 0;
 }
 
+// the tensors every forward / input-gradient call needs: A, Y and fp32 (or pre-packed) weights
+static int32_t check_data_call(const tpg_conv_desc* d, const tpg_tensor& A, const char* an, const tpg_tensor& Y,
+                               const char* yn, const tpg_tensor& w) {
+  int32_t rc;
+  if ((rc = check_tensor(A, d->dtype, an)) || (rc = check_tensor(Y, d->dtype, yn))) return rc;
+  if (!w.data || (w.dtype != TPG_F32 && !(d->flags & TPG_FLAG_WPACKED))) return fail(-13, "weight must be fp32");
+  return 0;
+}
+
 // ------------------------------------------------------------ pre-packed weights --
 // The packed image of (d, op) is the weight part of the op's workspace for the plan the
 // op picks on 16-byte aligned channels-last tensors: one region per problem, in plan order.
-static std::vector<Prob> pack_plan(const tpg_conv_desc* d, int32_t op) {
-  if (op == TPG_OP_FWD) return plan_fwd(d, fwd_composite(d, nullptr, nullptr));
-  return plan_bwd_data(d, bwd_data_composite(d, nullptr, nullptr));
+static void pack_plan(const PlanCtx& cx, const tpg_conv_desc* d, int32_t op, DataPlan* p) {
+  plan_probs(cx, d, op == TPG_OP_FWD, composite(d, nullptr, nullptr), p);
 }
 
 extern "C" size_t tpg_conv2d_packed_bytes(const tpg_conv_desc* d, int32_t op) {
-  ShareScope share_scope(d);
   if (check_desc(d) || (op != TPG_OP_FWD && op != TPG_OP_BWD_DATA)) return 0;
-  size_t b = 0;
-  for (const Prob& P : pack_plan(d, op)) b += std::max(P.wp_bytes, P.g_wp);
-  return b;
+  DataPlan p;
+  pack_plan(plan_ctx(d), d, op, &p);
+  return packed_bytes(p);
 }
 
 extern "C" size_t tpg_pack_job_bytes(void) { return sizeof(PackJob); }
 
 extern "C" int32_t tpg_conv2d_pack_jobs(const tpg_conv_desc* d, int32_t op, tpg_tensor w, void* wp, void* jobs,
                                         int32_t max_jobs) {
-  ShareScope share_scope(d);
   int32_t rc = check_desc(d);
   if (rc) return rc;
   if (op != TPG_OP_FWD && op != TPG_OP_BWD_DATA) return fail(-2, "pack: op must be fwd or bwd_data");
   if (!w.data || w.dtype != TPG_F32 || !wp || !jobs) return fail(-10, "pack: NULL / non-fp32 weight");
-  std::vector<Prob> v = pack_plan(d, op);
+  DataPlan p;
+  pack_plan(plan_ctx(d), d, op, &p);
   PackJob* out = reinterpret_cast<PackJob*>(jobs);
   int n = 0;
-  size_t off = 0;
-  for (Prob& P : v) {
-    const size_t region = std::max(P.wp_bytes, P.g_wp);
-    const bool has = P.halo ? P.h.ntaps > 0 : P.a.nunits > 0;
-    if (has) {
-      if (n >= max_jobs) return fail(-22, "pack: more than %d jobs", max_jobs);
-      PackJob& j = out[n++];
-      memset(&j, 0, sizeof(j));
-      j.k = P.pk;
-      j.k.W = reinterpret_cast<const float*>(w.data);
-      j.k.w_sa = w.stride[0]; j.k.w_sb = w.stride[1]; j.k.w_sr = w.stride[2]; j.k.w_ss = w.stride[3];
-      j.k.Wp = reinterpret_cast<char*>(wp) + off;
-      if (P.halo) {
-        j.kind = 1;
-        j.nks = P.h.nks; j.bn = P.h.BN; j.bnl = (P.h.BN + 127) / 128 * 128; j.ntiles = P.h.ntiles;
-        j.items = halo_steps(j.nks, j.k.ntaps, P.h.half) * j.ntiles * j.bnl * 4;
-      } else {
-        j.kind = 0;
-        j.items = j.k.Npad * j.k.nunits;
-      }
-      j.nblocks = cdiv(j.items, 256 * TPG_PACK_GROUPS);
+  for (const Prob& P : p.v) {
+    if (!(P.halo ? P.h.ntaps > 0 : P.a.nunits > 0)) continue;
+    if (n >= max_jobs) return fail(-22, "pack: more than %d jobs", max_jobs);
+    PackJob& j = out[n++];
+    memset(&j, 0, sizeof(j));
+    j.k = P.pk;
+    j.k.W = reinterpret_cast<const float*>(w.data);
+    j.k.w_sa = w.stride[0]; j.k.w_sb = w.stride[1]; j.k.w_sr = w.stride[2]; j.k.w_ss = w.stride[3];
+    j.k.Wp = reinterpret_cast<char*>(wp) + P.wp_off;
+    if (P.halo) {
+      j.kind = 1;
+      j.nks = P.h.nks; j.bn = P.h.BN; j.bnl = (P.h.BN + 127) / 128 * 128; j.ntiles = P.h.ntiles;
+      j.items = halo_steps(j.nks, j.k.ntaps, P.h.half) * j.ntiles * j.bnl * 4;
+    } else {
+      j.kind = 0;
+      j.items = j.k.Npad * j.k.nunits;
     }
-    off += region;
+    j.nblocks = cdiv(j.items, 256 * TPG_PACK_GROUPS);
   }
   return n;
 }
@@ -1028,76 +1023,79 @@ extern "C" int32_t tpg_pack_run(const void* jobs_dev, int32_t n, int64_t nblocks
                    "pack_run");
 }
 
+static const tpg_tensor g_none = {};
+
 extern "C" int32_t tpg_conv2d_fwd(const tpg_conv_desc* d, tpg_tensor x, tpg_tensor w, const float* bias,
                                   tpg_tensor residual, tpg_tensor y, void* ws, size_t ws_bytes, tpg_stream_t stream) {
-  ShareScope share_scope(d);
   int32_t rc = check_desc(d);
   if (rc) return rc;
-  if ((rc = check_tensor(x, d->dtype, "x")) || (rc = check_tensor(y, d->dtype, "y"))) return rc;
-  if (!w.data || (w.dtype != TPG_F32 && !(d->flags & TPG_FLAG_WPACKED))) return fail(-13, "weight must be fp32");
+  if ((rc = check_data_call(d, x, "x", y, "y", w))) return rc;
   if (residual.data && (rc = check_tensor(residual, d->dtype, "residual"))) return rc;
-  const bool comp = fwd_composite(d, &x, &y);
-  const bool packed = d->flags & TPG_FLAG_WPACKED;
-  if (!comp && big_taps(d)) return fail(-4, "%dx%d kernel: only the dense NHWC GEMM form is supported", d->kh, d->kw);
-  if (packed && comp != fwd_composite(d, nullptr, nullptr))
-    return fail(-21, "pre-packed weights assume a full-kernel GEMM; these tensors are not dense NHWC");
-  std::vector<Prob> v = plan_fwd(d, comp);
-  int bias_mod = (comp && d->transposed) ? d->out_c : 0;
-  if (comp && residual.data) return fail(-14, "residual not supported on a full-kernel conv");
-  return run_probs(v, d->dtype, x, w, bias, bias_mod, residual, d->res_scale, y, d->act, d->slope,
-                   reinterpret_cast<char*>(ws), ws_bytes, (hipStream_t)stream,
-                   packed ? reinterpret_cast<const char*>(w.data) : nullptr);
+  DataLayouts L;
+  L.A = &x; L.Y = &y; L.residual = residual.data != nullptr; L.packed = d->flags & TPG_FLAG_WPACKED;
+  DataPlan p;
+  if ((rc = plan_data(plan_ctx(d), d, TPG_OP_FWD, L, ws_bytes, &p))) return rc;
+  return run_data(p, x, w, bias, residual, y, nullptr, nullptr, nullptr, reinterpret_cast<char*>(ws), (hipStream_t)stream);
 }
-
-static int32_t bwd_data_impl(const tpg_conv_desc* d, tpg_tensor g, tpg_tensor w, tpg_tensor dx, void* ws,
-                             size_t ws_bytes, tpg_stream_t stream, HaloXA* xa);
 
 extern "C" int32_t tpg_conv2d_bwd_data(const tpg_conv_desc* d, tpg_tensor g, tpg_tensor w, tpg_tensor dx, void* ws,
                                        size_t ws_bytes, tpg_stream_t stream) {
-  ShareScope share_scope(d);
   int32_t rc = check_desc(d);
   if (rc) return rc;
   if (d->in_act != TPG_ACT_NONE) return fail(-33, "bwd_data: desc.in_act needs x (tpg_conv2d_bwd)");
-  return bwd_data_impl(d, g, w, dx, ws, ws_bytes, stream, nullptr);
+  if ((rc = check_data_call(d, g, "g", dx, "dx", w))) return rc;
+  DataLayouts L;
+  L.A = &g; L.Y = &dx; L.packed = d->flags & TPG_FLAG_WPACKED;
+  DataPlan p;
+  if ((rc = plan_data(plan_ctx(d), d, TPG_OP_BWD_DATA, L, ws_bytes, &p))) return rc;
+  return run_data(p, g, w, nullptr, (d->flags & TPG_FLAG_DX_ACCUM) ? dx : g_none, dx, nullptr, nullptr, nullptr,
+                  reinterpret_cast<char*>(ws), (hipStream_t)stream);
 }
 
-static int32_t bwd_data_impl(const tpg_conv_desc* d, tpg_tensor g, tpg_tensor w, tpg_tensor dx, void* ws,
-                             size_t ws_bytes, tpg_stream_t stream, HaloXA* xa) {
-  int32_t rc;
-  if ((rc = check_tensor(g, d->dtype, "g")) || (rc = check_tensor(dx, d->dtype, "dx"))) return rc;
-  const bool packed = d->flags & TPG_FLAG_WPACKED;
-  if (!w.data || (w.dtype != TPG_F32 && !packed)) return fail(-13, "weight must be fp32");
-  hipStream_t s = (hipStream_t)stream;
-  const bool comp = bwd_data_composite(d, &g, &dx);
-  if (!comp && big_taps(d)) return fail(-4, "%dx%d kernel: only the dense NHWC GEMM form is supported", d->kh, d->kw);
-  if (packed && comp != bwd_data_composite(d, nullptr, nullptr))
-    return fail(-21, "pre-packed weights assume a full-kernel GEMM; these tensors are not dense NHWC");
-  const char* pk = packed ? reinterpret_cast<const char*>(w.data) : nullptr;
-  std::vector<Prob> v = plan_bwd_data(d, comp);
-  tpg_tensor none;
-  memset(&none, 0, sizeof(none));
-  const bool refl = !comp && !d->transposed && d->pad_mode == TPG_PAD_REFLECT;
-  // DX_ACCUM: dx's entry values ride in as the epilogue's residual (read, then overwritten by
-  // the same thread): dx = dgrad + dx
-  const bool acc = d->flags & TPG_FLAG_DX_ACCUM;
-  if (acc && (comp || refl)) return fail(-32, "dx accumulation: zero-padded, non-GEMM-form geometries only");
-  if (!refl)
-    return run_probs(v, d->dtype, g, w, nullptr, 0, acc ? dx : none, acc ? 1.f : 0.f, dx, TPG_ACT_NONE, 0.f,
-                     reinterpret_cast<char*>(ws), ws_bytes, s, pk, nullptr, xa);
-  // reflect: gradient of the padded input into a dense NHWC temp, then fold onto dx
-  const size_t tmpb = reflect_tmp_bytes(d);
-  if (ws_bytes < tmpb) return fail(-20, "workspace too small");
-  const int PH = d->in_h + d->pad_t + d->pad_b, PW = d->in_w + d->pad_l + d->pad_r, Cp = (int)rup(d->in_c, 8);
-  tpg_tensor tmp;
-  memset(&tmp, 0, sizeof(tmp));
-  tmp.data = ws; tmp.dtype = d->dtype;
-  tmp.stride[0] = (int64_t)PH * PW * Cp; tmp.stride[1] = 1; tmp.stride[2] = (int64_t)PW * Cp; tmp.stride[3] = Cp;
-  rc = run_probs(v, d->dtype, g, w, nullptr, 0, none, 0.f, tmp, TPG_ACT_NONE, 0.f, reinterpret_cast<char*>(ws) + tmpb,
-                 ws_bytes - tmpb, s, pk);
+extern "C" int32_t tpg_conv2d_data_plan(const tpg_conv_desc* d, int32_t op, tpg_tensor a, tpg_tensor y, tpg_tensor m,
+                                        tpg_tensor g, tpg_tensor x, size_t ws_bytes, tpg_data_plan* out) {
+  if (!out) return fail(-1, "null plan");
+  int32_t rc = check_desc(d);
   if (rc) return rc;
-  TPG_GROUP_SYNC();
-  return hip_check(launch_reflect_fold(d->n, d->in_c, d->in_h, d->in_w, d->pad_t, d->pad_b, d->pad_l, d->pad_r, tmp, dx, s),
-                   "reflect_fold");
+  if (op != TPG_OP_FWD && op != TPG_OP_BWD_DATA && op != TPG_OP_BWD_DATA_MASKED)
+    return fail(-2, "data plan: op must be fwd, bwd_data or bwd_data_masked");
+  if ((rc = check_tensor(a, d->dtype, "a")) || (rc = check_tensor(y, d->dtype, "y"))) return rc;
+  const PlanCtx cx = plan_ctx(d);
+  DataLayouts L;
+  L.A = &a; L.Y = &y; L.packed = d->flags & TPG_FLAG_WPACKED;
+  if (op == TPG_OP_BWD_DATA_MASKED) { L.M = &m; L.G = &g; }
+  if (op != TPG_OP_FWD && d->in_act != TPG_ACT_NONE) L.X = &x;
+  DataPlan p;
+  if ((rc = plan_data(cx, d, op, L, ws_bytes, &p)))
+    return rc == -31 ? fail(-31, "masked input-gradient mode does not apply to this call") : rc;
+  if (p.v.size() > TPG_DATA_MAX_PROBS) return fail(-22, "data plan: more than %d problems", TPG_DATA_MAX_PROBS);
+  memset(out, 0, sizeof(*out));
+  out->nprobs = (int32_t)p.v.size();
+  out->flags = (p.comp ? TPG_DATA_COMPOSITE : 0) | (p.v[0].a.dil > 1 ? TPG_DATA_DILATED : 0) |
+               (p.refl ? TPG_DATA_REFLECT_FOLD : 0) | (p.masked ? TPG_DATA_MASKED : 0) | (p.xa ? TPG_DATA_IN_ACT : 0);
+  out->ws_bytes = data_workspace(cx, d, p.fwd);
+  out->packed_bytes = packed_bytes(p);
+  out->tmp_bytes = p.tmp_bytes;
+  out->sk_off = p.tmp_bytes + (p.packed ? 0 : p.sk_off);
+  for (size_t i = 0; i < p.v.size(); ++i) {
+    const Prob& P = p.v[i];
+    tpg_data_prob& o = out->prob[i];
+    o.taps = P.a.ntaps;
+    o.wp_off = (p.packed ? 0 : p.tmp_bytes) + P.wp_off;
+    o.wp_bytes = P.region();
+    o.sk_bytes = P.sk_bytes;
+    if (P.halo) {
+      const HaloArgs& h = P.h;
+      o.kernel = h.pw > 0 ? TPG_DATA_POINTWISE : TPG_DATA_HALO;
+      o.cfg = P.hcfg; o.th = h.TH; o.tw = h.TW; o.img = h.IMG; o.bn = h.BN; o.rows = P.hbm; o.halo_px = h.hcap;
+      o.ksteps = h.nks; o.ksplit = h.ksplit; o.kps = h.kps; o.paired = h.half; o.pw_tile = h.pw;
+    } else {
+      o.kernel = TPG_DATA_GENERIC;
+      o.cfg = P.cfg; o.bn = igemm_cfg_bn(P.cfg); o.rows = igemm_cfg_bm(P.cfg);
+      o.ksteps = P.a.nunits / (half16(d->dtype) ? 4 : 2); o.ksplit = P.a.ksplit; o.kps = P.a.kt_per_split;
+    }
+  }
+  return 0;
 }
 
 // ---- weight-gradient plans: kernel family, tile, pixel split and every launch argument that
@@ -1114,8 +1112,8 @@ struct WgradPlan {
 
 // Row-halo weight gradient (tpg_wgrad_rh.hip) for a stride-1 Conv2d: false when the shape is
 // not covered (the caller falls back).
-static bool plan_wgrad_rh(const tpg_conv_desc* d, const tpg_tensor& x, const tpg_tensor& g, const tpg_tensor& dw,
-                          WgradPlan* p) {
+static bool plan_wgrad_rh(const PlanCtx& cx, const tpg_conv_desc* d, const tpg_tensor& x, const tpg_tensor& g,
+                          const tpg_tensor& dw, WgradPlan* p) {
   if (!half16(d->dtype) || d->stride_h != 1 || d->stride_w != 1) return false;
   const int PH = d->out_h, PW = d->out_w, QH = d->in_h, QW = d->in_w;
   // row mode: one kernel row, 3/5/7 taps, 64-pixel row segments; image mode (algos 10, 11 and
@@ -1175,7 +1173,7 @@ static bool plan_wgrad_rh(const tpg_conv_desc* d, const tpg_tensor& x, const tpg
   } else {
     // pixel splits: whole rounds of resident blocks (one per CU, two for the <= 128-VGPR
     // tiles) against the fp32 atomics every extra split adds (~1.3 TB/s of added bytes)
-    const int resident = (img || a.cfg == 6 ? 256 : (a.cfg == 3 || (a.cfg != 0 && a.nt <= 4)) ? 512 : 256) / g_share;
+    const int resident = (img || a.cfg == 6 ? 256 : (a.cfg == 3 || (a.cfg != 0 && a.nt <= 4)) ? 512 : 256) / cx.share;
     const int taps = a.nr * a.nt;
     const double flops = 2.0 * a.tiles * bm * taps * bc * 64.0 * a.nkt;
     double best = -1;
@@ -1188,14 +1186,14 @@ static bool plan_wgrad_rh(const tpg_conv_desc* d, const tpg_tensor& x, const tpg
     }
   }
   ks = std::max(1, std::min(ks, a.nkt));
-  if (deterministic()) ks = 1;  // one block adds each dW element once
+  if (cx.det) ks = 1;  // one block adds each dW element once
   a.kt_per_split = cdiv(a.nkt, ks);
   a.ksplit = cdiv(a.nkt, a.kt_per_split);
   a.w_sa = dw.stride[0]; a.w_sb = dw.stride[1]; a.w_sr = dw.stride[2]; a.w_ss = dw.stride[3];
   // bias MFMAs spread over up to 16 / ksplit tiles: same-address atomics serialise (~50 ns
   // each), so blocks x splits adding into one dbias row must stay few
-  a.bshare = deterministic() ? 1 : std::max(1, std::min(a.ntb * a.nrg * cdiv(a.kw, a.nt), 16 / a.ksplit));
-  a.skip = g_rh_skip;
+  a.bshare = cx.det ? 1 : std::max(1, std::min(a.ntb * a.nrg * cdiv(a.kw, a.nt), 16 / a.ksplit));
+  a.skip = cx.skip;
   p->kernel = img ? TPG_WGRAD_IMAGE_HALO : TPG_WGRAD_ROW_HALO;
   p->cfg = a.cfg; p->bm = bm; p->bn = bc; p->tiles = a.tiles;
   return true;
@@ -1205,11 +1203,11 @@ static bool plan_wgrad_rh(const tpg_conv_desc* d, const tpg_tensor& x, const tpg
 // 6..12), else the flat DMA kernel on 16-byte aligned rows, else the generic kernel.
 static int32_t plan_bwd_filter(const tpg_conv_desc* d, const tpg_tensor& x, const tpg_tensor& g, const tpg_tensor& dw,
                                WgradPlan* p) {
-  ShareScope share_scope(d);
   int32_t rc = check_desc(d);
   if (rc) return rc;
   if ((rc = check_tensor(x, d->dtype, "x")) || (rc = check_tensor(g, d->dtype, "g"))) return rc;
   if (!dw.data || dw.dtype != TPG_F32) return fail(-13, "dw must be fp32");
+  const PlanCtx cx = plan_ctx(d);
   memset(p, 0, sizeof(*p));
   WgradArgs& a = p->a;
   p->p_is_x = d->transposed;
@@ -1218,7 +1216,7 @@ static int32_t plan_bwd_filter(const tpg_conv_desc* d, const tpg_tensor& x, cons
   const int PH = d->transposed ? d->in_h : d->out_h, PW = d->transposed ? d->in_w : d->out_w;
   const int QH = d->transposed ? d->out_h : d->in_h, QW = d->transposed ? d->out_w : d->in_w;
   const int Ca = d->transposed ? d->in_c : d->out_c, cb = d->transposed ? d->out_c : d->in_c;
-  const bool comp = d->transposed ? bwd_data_composite(d, &g, nullptr) : fwd_composite(d, &x, nullptr);
+  const bool comp = composite(d, &x, &g);
   if (!comp && big_taps(d)) return fail(-4, "%dx%d kernel: only the dense NHWC GEMM form is supported", d->kh, d->kw);
   a.p_sn = P.stride[0]; a.p_sh = P.stride[2]; a.p_sw = P.stride[3];
   a.q_sn = Q.stride[0]; a.q_sh = Q.stride[2]; a.q_sw = Q.stride[3];
@@ -1252,7 +1250,7 @@ static int32_t plan_bwd_filter(const tpg_conv_desc* d, const tpg_tensor& x, cons
   // kernel-row halo kernel (stride-1 Conv2d, bf16, 64-pixel row segments): algo 6, and the
   // default for untuned calls when it applies
   const bool rh_algo = d->algo >= 6 && d->algo <= 12;
-  if ((d->algo == 0 || rh_algo) && !comp && !d->transposed && plan_wgrad_rh(d, x, g, dw, p)) return 0;
+  if ((d->algo == 0 || rh_algo) && !comp && !d->transposed && plan_wgrad_rh(cx, d, x, g, dw, p)) return 0;
   if (rh_algo) return fail(-30, "wgrad: row-halo kernel does not apply to this shape");
   // pipelined DMA kernel when both operands are 16-byte aligned channels-last rows
   if (a.vec_p && a.vec_q) {
@@ -1276,14 +1274,14 @@ static int32_t plan_bwd_filter(const tpg_conv_desc* d, const tpg_tensor& x, cons
         if (best < 0 || cost < best) { best = cost; bm = c[0]; bn = c[1]; }
       }
       const int tiles = cdiv(a.Ca, bm) * (int)((ncols + bn - 1) / bn) * ngrid;
-      bks = std::max(1, cdiv(2048 / g_share, tiles));
+      bks = std::max(1, cdiv(2048 / cx.share, tiles));
       bks = std::min(bks, std::max(1, a.npix / (kp * 8)));
     }
     if (d->algo >= 1 && d->algo <= 5 && d->ksplit >= 1) {
       bm = cand[d->algo - 1][0]; bn = cand[d->algo - 1][1];
       bks = std::min(d->ksplit, nkt);
     }
-    if (deterministic()) bks = 1;
+    if (cx.det) bks = 1;
     a.pix_per_split = (int)rup(cdiv(a.npix, bks), kp);
     a.ksplit = cdiv(a.npix, a.pix_per_split);
     const int es = esize(d->dtype);
@@ -1305,7 +1303,7 @@ static int32_t plan_bwd_filter(const tpg_conv_desc* d, const tpg_tensor& x, cons
                 (int64_t)PH * PW > kp;
       a.dpy = kp / a.PW;
       a.dpx = kp % a.PW;
-      a.bshare = deterministic() ? 1 : std::max(1, std::min((int)((ncols + bn - 1) / bn) * ngrid, 16 / a.ksplit));
+      a.bshare = cx.det ? 1 : std::max(1, std::min((int)((ncols + bn - 1) / bn) * ngrid, 16 / a.ksplit));
       p->kernel = TPG_WGRAD_FLAT;
       p->cfg = wgrad2_cfg(bm, bn); p->bm = bm; p->bn = bn;
       p->tiles = cdiv(a.Ca, bm) * (int)((ncols + bn - 1) / bn) * ngrid;
@@ -1317,7 +1315,7 @@ static int32_t plan_bwd_filter(const tpg_conv_desc* d, const tpg_tensor& x, cons
   const int tiles = cdiv(a.Ca, bm) * cdiv(a.Cb, bn) * a.ntaps;
   int ks = std::max(1, cdiv(1536, tiles));
   ks = std::min(ks, std::max(1, a.npix / (32 * 16)));
-  if (deterministic()) ks = 1;
+  if (cx.det) ks = 1;
   a.pix_per_split = (int)rup(cdiv(a.npix, ks), 32);
   a.ksplit = cdiv(a.npix, a.pix_per_split);
   p->kernel = TPG_WGRAD_GENERIC;
@@ -1396,7 +1394,6 @@ extern "C" int32_t tpg_colsum_impl(int32_t n, int32_t c, int32_t h, int32_t w, t
 extern "C" int32_t tpg_conv2d_bwd(const tpg_conv_desc* d, tpg_tensor x, tpg_tensor w, tpg_tensor y, tpg_tensor gy,
                                   tpg_tensor g, tpg_tensor dx, tpg_tensor dw, float* dbias, void* ws, size_t ws_bytes,
                                   tpg_stream_t stream) {
-  ShareScope share_scope(d);
   int32_t rc = check_desc(d);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
@@ -1408,64 +1405,52 @@ extern "C" int32_t tpg_conv2d_bwd(const tpg_conv_desc* d, tpg_tensor x, tpg_tens
   const bool g_is_gy = !has_act && gy.dtype == d->dtype && vec_ok(gy, d->dtype);
   if (!g_is_gy && (rc = check_tensor(g, d->dtype, "g"))) return rc;
   const tpg_tensor& G = g_is_gy ? gy : g;
-  bool have_g = g_is_gy, bias_done = false, dx_done = false;
+  bool bias_done = false;
   const bool acc = dx.data && (d->flags & TPG_FLAG_DX_ACCUM);
   // desc.in_act: dx leaves as dx * in_act'(x) (the producer's activation backward)
-  HaloXA xa;
-  memset(&xa, 0, sizeof(xa));
   const bool xact = dx.data && d->in_act != TPG_ACT_NONE;
   if (xact) {
     if (d->in_act < TPG_ACT_NONE || d->in_act > TPG_ACT_RELU6) return fail(-2, "conv2d_bwd: bad in_act %d", d->in_act);
     if ((rc = check_tensor(x, d->dtype, "x")) || (rc = check_tensor(dx, d->dtype, "dx"))) return rc;
-    xa.X = x; xa.act = d->in_act; xa.slope = d->in_slope;
   }
-  if (acc && (bwd_data_composite(d, nullptr, nullptr) || (!d->transposed && d->pad_mode == TPG_PAD_REFLECT)))
+  if (acc && (composite(d, nullptr, nullptr) || (!d->transposed && d->pad_mode == TPG_PAD_REFLECT)))
     return fail(-32, "dx accumulation: zero-padded, non-GEMM-form geometries only");
-  // pre-packed weights that the input-gradient plan of these tensors cannot use: report it
-  // (-21) before anything is launched, so the caller's retry with fp32 weights adds nothing twice
-  if ((d->flags & TPG_FLAG_WPACKED) && dx.data &&
-      (!vec_ok(G, d->dtype) || bwd_data_composite(d, &G, &dx) != bwd_data_composite(d, nullptr, nullptr)))
-    return fail(-21, "pre-packed weights assume the halo kernel / dense NHWC; these tensors need another plan");
-  // 1. the input gradient with the activation' applied while its halo is staged (writes g)
+  // The input gradient is planned before anything is launched, so a status (-21: pre-packed
+  // weights these tensors cannot use) comes back before the bias gradient was added anywhere and
+  // the caller's retry with fp32 weights adds nothing twice.  Masked mode where the plan has it:
+  // the activation' applied while the halo is staged, g written on the way
   // (round 1 measured 42.1 ms/step with maps up to 64 x 64, 42.5 with every map, 43.0 with
-  // none; after the 512-row and stride-2 tiles -- which have no masked variant and now fall
-  // back to the separate pass -- every map measured 37.39 vs 37.54 / 37.56 at 64 x 64)
-  if (!have_g && dx.data && !d->transposed && d->stride_h == 1 && d->stride_w == 1 && d->pad_mode == TPG_PAD_ZERO &&
-      d->in_h == d->out_h && d->in_w == d->out_w && gy.dtype == d->dtype && y.dtype == d->dtype &&
-      dx.dtype == d->dtype && vec_ok(gy, d->dtype) && vec_ok(y, d->dtype) && vec_ok(g, d->dtype) &&
-      y.stride[0] == g.stride[0] && y.stride[2] == g.stride[2] && y.stride[3] == g.stride[3]) {
-    const bool packed = d->flags & TPG_FLAG_WPACKED;
-    if (w.data && (w.dtype == TPG_F32 || packed) && !bwd_data_composite(d, &gy, &dx)) {
-      std::vector<Prob> v = plan_bwd_data(d, false);
-      HaloMask mk;
-      mk.M = y; mk.G = g; mk.act = d->act; mk.slope = d->slope;
-      tpg_tensor none;
-      memset(&none, 0, sizeof(none));
-      rc = run_probs(v, d->dtype, gy, w, nullptr, 0, acc ? dx : none, acc ? 1.f : 0.f, dx, TPG_ACT_NONE, 0.f,
-                     reinterpret_cast<char*>(ws), ws_bytes, s, packed ? reinterpret_cast<const char*>(w.data) : nullptr,
-                     &mk, xact ? &xa : nullptr);
-      if (rc == 0) have_g = dx_done = true;
-      else if (rc != -31) return rc;
+  // none; after the 512-row and stride-2 tiles -- which have no masked variant and take the
+  // separate pass -- every map measured 37.39 vs 37.54 / 37.56 at 64 x 64)
+  DataPlan dp;
+  if (dx.data) {
+    if ((rc = check_data_call(d, G, "g", dx, "dx", w))) return rc;
+    const PlanCtx cx = plan_ctx(d);
+    DataLayouts L;
+    L.A = &gy; L.Y = &dx; L.M = &y; L.G = &g; L.X = xact ? &x : nullptr; L.packed = d->flags & TPG_FLAG_WPACKED;
+    rc = g_is_gy ? -31 : plan_data(cx, d, TPG_OP_BWD_DATA_MASKED, L, ws_bytes, &dp);
+    if (rc == -31) {
+      L.A = &G;
+      rc = plan_data(cx, d, TPG_OP_BWD_DATA, L, ws_bytes, &dp);
     }
+    if (rc) return rc;
   }
-  // 2. otherwise the activation backward pass materialises g (and sums the bias when there is
+  // otherwise the activation backward pass materialises g (and sums the bias when there is
   // no weight gradient: with one, the weight-gradient launch sums it, the same order whether
   // the caller runs the weight gradient here or as a second call on another stream)
-  if (!have_g) {
+  if (!g_is_gy && !dp.masked) {
     // (ConvTranspose2d: its weight-gradient kernels never take the bias -- it would cost a
     // separate column-sum launch, so this pass keeps it)
     float* db = (dw.data && !d->transposed) ? nullptr : dbias;
     rc = hip_check(do_act_bwd(d->n, d->out_c, d->out_h, d->out_w, d->act, d->slope, gy, y, g, db, s),
                    "act_bwd");
     if (rc) return rc;
-    have_g = true;
     bias_done = db != nullptr;
   }
-  if (dx.data && !dx_done) {
-    xa.applied = false;
-    if ((rc = bwd_data_impl(d, G, w, dx, ws, ws_bytes, stream, xact ? &xa : nullptr))) return rc;
-  }
-  if (xact && !xa.applied) {  // (plans whose epilogue cannot take it: one in-place pass over dx)
+  if (dx.data && (rc = run_data(dp, dp.masked ? gy : G, w, nullptr, acc ? dx : g_none, dx, &y, &g, &x,
+                                reinterpret_cast<char*>(ws), s)))
+    return rc;
+  if (xact && !dp.xa) {  // (plans whose epilogue cannot take it: one in-place pass over dx)
     rc = hip_check(do_act_bwd(d->n, d->in_c, d->in_h, d->in_w, d->in_act, d->in_slope, dx, x, dx, nullptr, s),
                    "act_bwd (in_act)");
     if (rc) return rc;

@@ -772,14 +772,30 @@ static int launch_halo_t(const HaloArgs& a, dim3 grid, hipStream_t s) {
 #define TPG_HALO_CFGS_S2(X)
 #endif
 
-int launch_halo(const HaloArgs& a, int dtype, int cfg, hipStream_t s, bool mask) {
-  dim3 grid((a.N * a.tiles_h * a.tiles_w + a.IMG - 1) / a.IMG, a.ntiles, a.ksplit);
+// Whether config `cfg` has a build that takes the plan: a known id whose halo class holds
+// a.hcap pixels, and for the masked mode one of the 256-row stride-1 configs.  The planner asks
+// before it settles on this kernel; the launcher keeps the test as its guard.
+bool halo_accepts(const HaloArgs& a, int cfg, bool mask) {
   // mask mode: one k-step's y chunks must land (LDS-DMA issued at tap 0) before its halo is
   // staged (last tap): at least two taps, the 3-slot ring, whole 16-pixel DMA rows
-  if (mask && (a.ntaps < 2 || a.hcap % 16 || a.SH != 1 || a.SW != 1)) return -1;
+  if (mask && (a.ntaps < 2 || a.hcap % 16 || a.SH != 1 || a.SW != 1)) return false;
+#define X(id, HL_, BN_, WM_, WN_) \
+  if (cfg == (id)) return a.hcap <= HL_ * 128;
+  TPG_HALO_CFGS(X)
+#undef X
+#define X(id, HL_, BN_, WM_, WN_) \
+  if (cfg == (id)) return a.hcap <= HL_ * 128 && !mask;
+  TPG_HALO_CFGS512(X)
+  TPG_HALO_CFGS_S2(X)
+#undef X
+  return false;
+}
+
+int launch_halo(const HaloArgs& a, int dtype, int cfg, hipStream_t s, bool mask) {
+  if (!halo_accepts(a, cfg, mask)) return -1;
+  dim3 grid((a.N * a.tiles_h * a.tiles_w + a.IMG - 1) / a.IMG, a.ntiles, a.ksplit);
 #define X(id, HL_, BN_, WM_, WN_)                                                          \
   if (cfg == (id)) {                                                                       \
-    if (a.hcap > HL_ * 128) return -1;                                                     \
     if (mask) return dtype == 1 ? launch_halo_t<1, HL_, BN_, WM_, WN_, true>(a, grid, s)    \
                    : dtype == 2 ? launch_halo_t<2, HL_, BN_, WM_, WN_, true>(a, grid, s)    \
                                 : launch_halo_t<0, HL_, BN_, WM_, WN_, true>(a, grid, s);   \
@@ -791,7 +807,6 @@ int launch_halo(const HaloArgs& a, int dtype, int cfg, hipStream_t s, bool mask)
 #undef X
 #define X(id, HL_, BN_, WM_, WN_)                                                          \
   if (cfg == (id)) {                                                                       \
-    if (a.hcap > HL_ * 128 || mask) return -1;                              \
     return dtype == 1 ? launch_halo_t<1, HL_, BN_, WM_, WN_, false, 512>(a, grid, s)       \
          : dtype == 2 ? launch_halo_t<2, HL_, BN_, WM_, WN_, false, 512>(a, grid, s)       \
                       : launch_halo_t<0, HL_, BN_, WM_, WN_, false, 512>(a, grid, s);      \
@@ -800,7 +815,6 @@ int launch_halo(const HaloArgs& a, int dtype, int cfg, hipStream_t s, bool mask)
 #undef X
 #define X(id, HL_, BN_, WM_, WN_)                                                          \
   if (cfg == (id)) {                                                                       \
-    if (a.hcap > HL_ * 128 || mask) return -1;                              \
     return dtype == 1 ? launch_halo_t<1, HL_, BN_, WM_, WN_, false>(a, grid, s)            \
          : dtype == 2 ? launch_halo_t<2, HL_, BN_, WM_, WN_, false>(a, grid, s)            \
                       : launch_halo_t<0, HL_, BN_, WM_, WN_, false>(a, grid, s);           \

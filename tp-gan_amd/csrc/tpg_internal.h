@@ -534,6 +534,10 @@ int halo_cfg(int hl, int bn);
 size_t halo_lds_bytes(int hcap, int bn, int rs = 3, int bm = 256);
 int halo_cfg512(int bn);
 int launch_halo(const HaloArgs& a, int dtype, int cfg, hipStream_t s, bool mask = false);
+// what launch_halo / launch_pw refuse (-1), as host predicates: the planner calls them so that a
+// finished plan never meets the refusal (pw_accepts reads A's geometry and strides from a)
+bool halo_accepts(const HaloArgs& a, int cfg, bool mask);
+bool pw_accepts(const HaloArgs& a, int dtype);
 // pointwise (1x1) GEMM kernel on a one-tap halo plan (a.pw = tile config 1..4: 128x128, 128x64,
 // 64x128, 64x64 rows x output channels); same packed weights, epilogue and split-K slices
 int launch_pw(const HaloArgs& a, int dtype, hipStream_t s);

@@ -339,29 +339,39 @@ static constexpr int PW_BN[4] = {128, 64, 128, 64};
 int pw_tile_bm(int cfg) { return cfg >= 1 && cfg <= 4 ? PW_BM[cfg - 1] : 0; }
 int pw_tile_bn(int cfg) { return cfg >= 1 && cfg <= 4 ? PW_BN[cfg - 1] : 0; }
 
+static int64_t pw_blocks(const HaloArgs& a, int bm, int bn) {
+  const int M = a.N * a.JH * a.JW;
+  return (int64_t)((M + bm - 1) / bm) * ((a.Nout + bn - 1) / bn) * a.ksplit;
+}
+
 template <int DT, int BM, int BN>
 static int launch_pw_t(const HaloArgs& a, hipStream_t s) {
   auto k = pw_kernel<DT, BM, BN>;
   constexpr int lds = pw_lds_bytes(BM, BN);
   static bool once = ((void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);
   (void)once;
-  const int M = a.N * a.JH * a.JW;
-  const int64_t blocks = (int64_t)((M + BM - 1) / BM) * ((a.Nout + BN - 1) / BN) * a.ksplit;
-  if (blocks <= 0 || blocks >= (1ll << 31)) return -1;
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), lds, s, a);
+  hipLaunchKernelGGL(k, dim3((unsigned)pw_blocks(a, BM, BN)), dim3(256), lds, s, a);
   return (int)hipGetLastError();
 }
 
-int launch_pw(const HaloArgs& a, int dtype, hipStream_t s) {
-  // the kernel's assumptions (the planner only picks it when they hold): whole
-  // 32-channel k-steps, a planner tile at least as wide as this one, 32-bit byte offsets
+// The kernel's assumptions: whole 32-channel k-steps, a planner tile at least as wide as this
+// one, 32-bit byte offsets into A (its geometry and strides filled in), a 31-bit grid.  The
+// planner asks before it settles on this kernel; the launcher keeps the test as its guard.
+bool pw_accepts(const HaloArgs& a, int dtype) {
   if (a.ntaps < 1 || a.ntaps > TPG_MAX_TAPS || a.dil > 1 || a.C % 32 || (dtype != 1 && dtype != 2) || a.pw < 1 ||
       a.pw > 4 || a.HW < 1 || a.HW >= (1 << 16))
-    return -1;
+    return false;
   const int bm = PW_BM[a.pw - 1], bn = PW_BN[a.pw - 1];
-  if (a.BN < bn || a.BN % bn) return -1;
+  if (a.BN < bn || a.BN % bn) return false;
   const int64_t ext = ((int64_t)(a.N - 1) * a.a_sn + (int64_t)(a.A_H - 1) * a.a_sh + (int64_t)(a.A_W - 1) * a.a_sw + a.C) * 2;
-  if (ext >= 0x7FFFFFF0ll || a.a_sn < 0 || a.a_sh < 0 || a.a_sw < 0) return -1;
+  if (ext >= 0x7FFFFFF0ll || a.a_sn < 0 || a.a_sh < 0 || a.a_sw < 0) return false;
+  const int64_t blocks = pw_blocks(a, bm, bn);
+  return blocks > 0 && blocks < (1ll << 31);
+}
+
+int launch_pw(const HaloArgs& a, int dtype, hipStream_t s) {
+  if (!pw_accepts(a, dtype)) return -1;
+  const int bm = PW_BM[a.pw - 1], bn = PW_BN[a.pw - 1];
 #define PW_L(BM_, BN_)                                                                          \
   if (bm == BM_ && bn == BN_) return dtype == 1 ? launch_pw_t<1, BM_, BN_>(a, s) : launch_pw_t<2, BM_, BN_>(a, s);
   PW_L(128, 128) PW_L(128, 64) PW_L(64, 128) PW_L(64, 64)

@@ -21,7 +21,7 @@ TPG_F32, TPG_BF16, TPG_F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_RELU6 = 0, 1, 2, 3
 SSD_TERMS, SSD_MAXN = 16, 4096  # (include/tpgan.h TPG_SSD_TERMS / TPG_SSD_MAXN)
 PAD_ZERO, PAD_REFLECT = 0, 1
-OP_FWD, OP_BWD_DATA, OP_BWD_FILTER = 0, 1, 2
+OP_FWD, OP_BWD_DATA, OP_BWD_FILTER, OP_BWD_DATA_MASKED = 0, 1, 2, 3
 
 
 class TpgTensor(ctypes.Structure):
@@ -46,6 +46,25 @@ class WgradPlan(ctypes.Structure):  # tpg_wgrad_plan
 WGRAD_KERNELS = ("generic", "flat", "row_halo", "image_halo")  # (TPG_WGRAD_*, by value)
 
 
+class DataProb(ctypes.Structure):  # tpg_data_prob
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "kernel", "cfg", "th", "tw", "img", "bn", "rows", "halo_px", "taps", "ksteps", "ksplit", "kps", "paired",
+        "pw_tile")] + [(n, ctypes.c_uint64) for n in ("wp_off", "wp_bytes", "sk_bytes")]
+
+
+DATA_MAX_PROBS = 16
+
+
+class DataPlan(ctypes.Structure):  # tpg_data_plan
+    _fields_ = [("nprobs", ctypes.c_int32), ("flags", ctypes.c_int32)] + [
+        (n, ctypes.c_uint64) for n in ("ws_bytes", "packed_bytes", "tmp_bytes", "sk_off")] + [
+        ("prob", DataProb * DATA_MAX_PROBS)]
+
+
+DATA_KERNELS = ("generic", "halo", "pointwise")  # (TPG_DATA_*, by value)
+DATA_COMPOSITE, DATA_DILATED, DATA_REFLECT_FOLD, DATA_MASKED, DATA_IN_ACT = 1, 2, 4, 8, 16
+
+
 class L1Seg(ctypes.Structure):  # tpg_l1_seg
     _fields_ = [("n", ctypes.c_int32), ("c", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
                 ("a", TpgTensor), ("b", TpgTensor), ("da", TpgTensor), ("weight", ctypes.c_float)]
@@ -68,6 +87,8 @@ EXPORTS = {
                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "tpg_conv2d_wgrad_plan": (ctypes.c_int32, [ctypes.POINTER(ConvDesc), TpgTensor, TpgTensor, TpgTensor,
                                                ctypes.POINTER(WgradPlan)]),
+    "tpg_conv2d_data_plan": (ctypes.c_int32, [ctypes.POINTER(ConvDesc), ctypes.c_int32] + [TpgTensor] * 5 +
+                             [ctypes.c_size_t, ctypes.POINTER(DataPlan)]),
     "tpg_conv2d_bwd": (ctypes.c_int32, [ctypes.POINTER(ConvDesc), TpgTensor, TpgTensor, TpgTensor, TpgTensor,
                                         TpgTensor, TpgTensor, TpgTensor, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_size_t, ctypes.c_void_p]),
