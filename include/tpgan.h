@@ -102,7 +102,11 @@ typedef struct tpg_conv_desc {
                                      128x32, 64x32 (2x2 / 3x3 kernels, output width 8/16/32/64·m,
                                      64 / width dividing the height); 12 = kernel-row halo kernel,
                                      tile 256x32 (one a-tile up to 256 output channels: dY read
-                                     once per b-tile); -30 when not covered */
+                                     once per b-tile); 13 = kernel-row halo kernel, dense tile
+                                     80 x (7 taps x 80): one block per kernel row of a 7-wide
+                                     kernel with at most 80 channels on each side, a tap per
+                                     wave (16-bit, output width a multiple of 64; no dead-block
+                                     skip); -30 when not covered */
   int32_t flags;                  /* TPG_FLAG_*: WPACKED = w.data is the image tpg_conv2d_pack_jobs /
                                      tpg_pack_run produced for this descriptor and op */
   int32_t data_ksplit;            /* 0 = automatic; >= 1 forces the k-step split of the forward and

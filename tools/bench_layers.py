@@ -124,7 +124,7 @@ def timed(fn, iters, graph):
     return e0.elapsed_time(e1) / iters
 
 
-SWEEP = {"algos": tuple(range(1, 13)), "ks": (1, 2, 4, 8, 16, 32, 64)}  # (--wg-sweep candidates)
+SWEEP = {"algos": tuple(range(1, 14)), "ks": (1, 2, 4, 8, 16, 32, 64)}  # (--wg-sweep candidates)
 
 
 def run(name, s, iters, passes, sweep=False, wg_algo=0, graph=False, dsplits=(), dalgo=0):

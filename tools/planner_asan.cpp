@@ -371,7 +371,7 @@ int main(int argc, char** argv) {
     d.ksplit = rnd() % 3 ? 0 : 1 + rnd() % 16;
     d.data_ksplit = rnd() % 3 ? 0 : 1 + rnd() % 64;
     d.data_algo = rnd() % 3 ? 0 : (int)(rnd() % 4) - 1;
-    d.algo = rnd() % 3 ? 0 : (int)(rnd() % 14) - 1;
+    d.algo = rnd() % 3 ? 0 : (int)(rnd() % 15) - 1;
     d.flags = rnd() % 8;
     if (d.transposed) {
       d.out_h = (d.in_h - 1) * d.stride_h - d.pad_t - d.pad_b + d.kh + (int)(rnd() % d.stride_h);

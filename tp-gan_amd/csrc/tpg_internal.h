@@ -236,7 +236,8 @@ struct WgradRHArgs {
   int nrg;                    // kernel-row groups = ceil(kh / nr); tap-column groups = ceil(kw / nt)
   int tw;                     // k-tile width (64 px = (64 / tw) rows of tw)
   int cfg;                    // tile: 0 = 128 x 64, 1 = 128 x 32, 2 = 64 x 64, 3 = 64 x 32 (a x b);
-                              // image mode: 4 = 128 x 32, 5 = 64 x 32
+                              // image mode: 4 = 128 x 32, 5 = 64 x 32; 6 = 256 x 32; 7 = the dense
+                              // 80 x (7 taps x 80) tap-per-wave tile (wgrad_rd_kernel)
   int nta, ntb, tiles;        // tiles = nta * ntb * kh * groups
   int nkt, kt_per_split, ksplit;
   float* dW;

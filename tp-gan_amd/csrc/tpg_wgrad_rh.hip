@@ -17,6 +17,7 @@
 // tiles that read the same dY / X rows run together on one XCD's L2.
 #include "tpg_internal.h"
 #include <type_traits>
+#include <utility>
 
 // timing ablations (tools only; never in the product build): bit 1 no LDS-DMA, 2 no barrier,
 // 4 no MFMA, 8 no fragment reads
@@ -457,8 +458,372 @@ void wgrad_rh_kernel(const WgradRHArgs p) {
   }
 }
 
+// (helpers of the dense tile below)
+__device__ __forceinline__ s16x4 rd_tr_read_a(unsigned a, int off) {
+  s16x4 v;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(a), "i"(off));
+  return v;
+}
+template <int... I, class F>
+__device__ __forceinline__ void rd_static_for(std::integer_sequence<int, I...>, F&& f) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+// Fragment-read schedule of a tap wave's k-tile: T = NS x MR x NR MFMAs, m-major inside a
+// substep.  Before MFMA 0: the first A row fragment and the first substep's NR B fragments
+// (two reads each).  After the first MFMA of a row: the next row's A fragment.  After MFMA i of
+// a substep that is not the last: the next substep's B reads i * 2 NR / M .. (i + 1) * 2 NR / M.
+// LDS reads return in order, so MFMA t waits for lgkmcnt(issued - 1 - need): the reads issued
+// before it, less those up to the last one it needs.
+struct RdSched {
+  static constexpr int NS = 2, MR = 5, NR = 5, M = MR * NR, T = NS * M;
+  int issued, need;
+};
+constexpr RdSched rd_sched(int t_) {
+  int ia[RdSched::NS * RdSched::MR] = {}, ib[RdSched::NS][RdSched::NR] = {};  // last read of each fragment
+  int n = 2;
+  ia[0] = n - 1;
+  for (int j = 0; j < RdSched::NR; ++j) { n += 2; ib[0][j] = n - 1; }
+  for (int t = 0; t < t_; ++t) {
+    const int ks = t / RdSched::M, i = t % RdSched::M, m = i / RdSched::NR, j = i % RdSched::NR;
+    const int gr = ks * RdSched::MR + m;
+    if (j == 0 && gr + 1 < RdSched::NS * RdSched::MR) { n += 2; ia[gr + 1] = n - 1; }
+    if (ks + 1 < RdSched::NS)
+      for (int rr = i * 2 * RdSched::NR / RdSched::M; rr < (i + 1) * 2 * RdSched::NR / RdSched::M; ++rr)
+        ib[ks + 1][rr >> 1] = n++;
+  }
+  const int ks = t_ / RdSched::M, i = t_ % RdSched::M;
+  const int a = ia[ks * RdSched::MR + i / RdSched::NR], b = ib[ks][i % RdSched::NR];
+  return RdSched{n, a > b ? a : b};
+}
+
+// ---- Dense tap-per-wave tile (desc.algo 13, tile id 7): 7-wide kernels with at most 80 channels
+// on each side.  The tiles above cut 75 dY channels into two 64-row tiles and 75 X channels
+// into three 32-column tiles per tap (46 % of the MFMA tile space live, and three of the four
+// wave rows of the second row tile idle behind the dead-block skip).  Here a block owns one
+// kernel row r, all 7 taps and an 80 x 80 channel tile: 5 x 35 MFMA blocks, all live for 65..80
+// channels.  Wave s (0..6) owns tap s, 5 x 5 blocks = 100 accumulator registers; the eighth
+// wave has no tap: it issues its share of the DMA and sums the bias gradient (dY fragments
+// against ones, as above).  Every tap wave reads the same five dY row fragments and the X halo
+// shifted by its tap: 20 transposed reads per 25 MFMAs (0.8, against 1.9 on the 64 x 32 tile).
+//
+// LDS rows: the 160 live bytes of a pixel are kept in a 256-byte row with the 256-byte chunk
+// swizzle above; the DMA fetches only the 10 live 16-byte chunks of a row (lanes of the other
+// 6 give an out-of-range offset, which moves nothing from memory and stores zeros).  Stage =
+// 64 dY rows + 72 halo rows = 34 KB, ring 102 KB, one block per CU.  Bank argument: a
+// transposed read takes, per 32-lane half, two 16-lane groups of 4 rows x 32 bytes (chunks
+// 2c, 2c + 1 of rows R + q and R + 8 + q, q = 0..3, the same R for the whole half: R = 8 x (first
+// group of the half) + K half + substep + tap).  A row is exactly one 256-byte bank row, so the
+// banks of a 32-byte piece depend only on its swizzled chunk pair c ^ ((row & 3) | (bit 3 of row)
+// << 2).  Rows R + q, q = 0..3, differ in row & 3; rows R + q and R + 8 + q differ in bit 3 whatever R
+// is; so the 8 pieces of a half lie on 8 different chunk pairs for every tap shift: no conflict,
+// for dY and for X.  A 160-byte row image would save 38 % of the ring, which nothing here needs.
+//
+// Pipeline, epilogue and block order are those of wgrad_rh_kernel.  18 X pieces over 8 waves:
+// waves 0 and 1 issue 5 DMA instructions per k-tile, the others 4, and each waits on its own count.
+template <int DT>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1)))
+void wgrad_rd_kernel(const WgradRHArgs p) {
+  constexpr int KP = 64, NT = 7, BM = 80, BC = 80, RB = 256;
+  constexpr int MREP = BM / 16, NREP = BC / 16;
+  constexpr int BYTES_A = KP * RB;
+  constexpr int HROWS = 72;                  // >= 64 + NT - 1 halo pixels, whole 1 KiB pieces
+  constexpr int PB = HROWS * RB / 1024;      // X pieces: 18 = 2 per wave + one more on waves 0, 1
+  constexpr int STAGE = BYTES_A + HROWS * RB;
+  static_assert(PB > 16 && PB <= 24 && KP * RB == 16 * 1024, "dma pieces");
+
+  extern __shared__ __attribute__((aligned(16))) char lds[];  // [3][STAGE]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  // (XCD-aware block order as above; logical = split * tiles + kernel row)
+  const int nblk = gridDim.x, full = nblk & ~7, bid = blockIdx.x;
+  const int L = bid < full ? (bid & 7) * (full >> 3) + (bid >> 3) : bid;
+  const int r0 = L % p.tiles, split = L / p.tiles;
+  const int kt0 = split * p.kt_per_split;
+  const int nkt = min(p.nkt, kt0 + p.kt_per_split) - kt0;
+  if (nkt <= 0) return;
+  // bias gradient: k-tile kt of the split is summed by the block of kernel row kt % bshare
+  const bool has_bias = p.dbias != nullptr && r0 < p.bshare;
+  const bool tap_wave = wave < NT;
+
+  const int segs = p.PW / KP;
+  int n = kt0 / (p.PH * segs);
+  int rem = kt0 - n * p.PH * segs;
+  int py = rem / segs;
+  int px0 = (rem % segs) * KP;
+
+  const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.P), 0, p.p_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rQ = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.Q), 0, p.q_bytes, 0x00020000);
+  constexpr unsigned OOB = 0x80000000u;
+
+  // per-lane constants of the DMA pieces (4 rows x 16 chunks each)
+  //   dY piece 2 * wave + j: pixels (2 * wave + j) * 4 .. + 3 of the k-tile
+  unsigned aoff[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int row = (wave * 2 + j) * 4 + (lane >> 4), pc = lane & 15;
+    const int c = (pc ^ rh_swz<RB>(row)) << 3;
+    aoff[j] = c < p.Ca ? (unsigned)((row * p.p_sw + c) * 2) : OOB;
+  }
+  //   X piece j * 8 + wave (< PB): halo pixels (j * 8 + wave) * 4 .. + 3
+  int bhx[3], bch[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int row = (j * 8 + wave) * 4 + (lane >> 4), pc = lane & 15;
+    const int c = (pc ^ rh_swz<RB>(row)) << 3;
+    bhx[j] = row - p.pl;                       // + px0 = X column
+    bch[j] = (c < p.Cb && row < KP + NT - 1) ? c : -1;
+  }
+  const bool third = wave < PB - 16;           // this wave issues a third X piece
+
+  auto issue = [&](int slot, int n_, int py_, int px_) {
+    char* st = lds + slot * STAGE;
+    const int sbase = (n_ * p.p_sn + py_ * p.p_sh + px_ * p.p_sw) * 2;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const unsigned vo = aoff[j];
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rP, (__attribute__((address_space(3))) void*)(st + (wave * 2 + j) * 1024),
+                                               16, vo, sbase, 0, 0);
+    }
+    int qy = py_ + r0 - p.pt;
+    const bool yok = p.pad_mode || (unsigned)qy < (unsigned)p.QH;
+    if (p.pad_mode) qy = rh_refl(qy, p.QH);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      if (j == 2 && !third) break;
+      int qx = px_ + bhx[j];
+      bool ok = bch[j] >= 0 && yok;
+      if (p.pad_mode) qx = rh_refl(qx, p.QW);
+      else ok = ok && (unsigned)qx < (unsigned)p.QW;
+      const unsigned off = ok ? (unsigned)((n_ * p.q_sn + qy * p.q_sh + qx * p.q_sw + bch[j]) * 2) : OOB;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rQ, (__attribute__((address_space(3))) void*)(st + BYTES_A + (j * 8 + wave) * 1024),
+                                               16, off, 0, 0, 0);
+    }
+  };
+
+  // (no dead-block skip here: the tile is meant for 65..80 channels, where every block is live;
+  // blocks past Ca / Cb multiply the zeros their DMA lanes stored.  The scalar branch around each
+  // MFMA also kept the accumulators from staying in place: a second set of 100 registers.)
+  const int g = lane >> 4, l16 = lane & 15;
+  const int q = l16 >> 2, p4 = l16 & 3;
+  const bool bias_wave = has_bias && !tap_wave;
+  f32x4 acc[MREP][NREP], accb[MREP];
+#pragma unroll
+  for (int m = 0; m < MREP; ++m) {
+    accb[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NREP; ++j) acc[m][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4r{one_pair<DT>(), one_pair<DT>(), one_pair<DT>(), one_pair<DT>()});
+
+  // per-lane LDS byte offsets of the fragment reads (as in row mode above: the substep's + 32
+  // rows and, for dY, the K half's + 4 rows leave the swizzle alone and go into the offset
+  // field; the tap shift does not, so the X bases carry it)
+  const int tap = tap_wave ? wave : 0;
+  // (absolute LDS addresses of ring slot 0; moved from slot to slot in place below, so the
+  // k-tile loop holds MREP + 2 * NREP address registers and no per-slot copies of them)
+  unsigned abase[MREP], bbase[NREP][2];
+  const unsigned lds0 = lds_addr(lds);
+#pragma unroll
+  for (int m = 0; m < MREP; ++m) {
+    const int col = m * 16 + 4 * p4, row = 8 * g + q;
+    abase[m] = lds0 + row * RB + (((col >> 3) ^ rh_swz<RB>(row)) << 4) + (col & 7) * 2;
+  }
+#pragma unroll
+  for (int j = 0; j < NREP; ++j)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int col = j * 16 + 4 * p4;
+      const int row = 8 * g + 4 * h + q + tap;  // halo row = pixel + tap
+      bbase[j][h] = lds0 + BYTES_A + row * RB + (((col >> 3) ^ rh_swz<RB>(row)) << 4) + (col & 7) * 2;
+    }
+  auto pin_bases = [&]() {
+#pragma unroll
+    for (int m = 0; m < MREP; ++m) asm volatile("" : "+v"(abase[m]));
+#pragma unroll
+    for (int j = 0; j < NREP; ++j) {
+      asm volatile("" : "+v"(bbase[j][0]));
+      asm volatile("" : "+v"(bbase[j][1]));
+    }
+  };
+  pin_bases();
+
+  constexpr int NS = KP / 32;
+  static_assert(NS == RdSched::NS && MREP == RdSched::MR && NREP == RdSched::NR, "fragment read schedule");
+  // a tap wave's k-tile: NS x MREP x NREP MFMAs, m-major, every one behind a counted wait for its
+  // own two fragments (rd_sched).  A row fragments roll through two buffers, the B fragments
+  // of the next substep land in a second set while this one is used: 48 fragment registers
+  // (both substeps' fragments held whole, as wgrad_rh_kernel does, are 80 and spilled).
+  auto compute = [&]() {
+    s16x4 fa[2][2], fb[2][NREP][2];
+    auto rd_a = [&](auto grc) {  // dY fragment of global row gr = ks * MREP + m
+      constexpr int gr = decltype(grc)::value, ks = gr / MREP, m = gr % MREP;
+      fa[gr & 1][0] = rd_tr_read_a(abase[m], (32 * ks) * RB);
+      fa[gr & 1][1] = rd_tr_read_a(abase[m], (32 * ks + 4) * RB);
+    };
+    auto rd_b = [&](auto ksc, auto rrc) {  // read rr of substep ks: half rr & 1 of X fragment rr >> 1
+      constexpr int ks = decltype(ksc)::value, rr = decltype(rrc)::value;
+      fb[ks & 1][rr >> 1][rr & 1] = rd_tr_read_a(bbase[rr >> 1][rr & 1], 32 * ks * RB);
+    };
+    rd_a(std::integral_constant<int, 0>{});
+    rd_static_for(std::make_integer_sequence<int, 2 * NREP>{},
+                  [&](auto rrc) { rd_b(std::integral_constant<int, 0>{}, rrc); });
+    __builtin_amdgcn_sched_barrier(0);
+    rd_static_for(std::make_integer_sequence<int, RdSched::T>{}, [&](auto tc) {
+      constexpr int t = decltype(tc)::value, ks = t / RdSched::M, i = t % RdSched::M, m = i / NREP, j = i % NREP;
+      constexpr int gr = ks * MREP + m;
+      constexpr RdSched sc = rd_sched(t);
+      constexpr int w = sc.issued - 1 - sc.need < 15 ? sc.issued - 1 - sc.need : 15;
+      static_assert(w >= 0, "a fragment is read before its MFMA");
+      asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(w) : "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      const bf16x8 av = __builtin_bit_cast(bf16x8, __builtin_shufflevector(fa[gr & 1][0], fa[gr & 1][1],
+                                                                           0, 1, 2, 3, 4, 5, 6, 7));
+      const bf16x8 bv = __builtin_bit_cast(bf16x8, __builtin_shufflevector(fb[ks & 1][j][0], fb[ks & 1][j][1],
+                                                                           0, 1, 2, 3, 4, 5, 6, 7));
+      acc[m][j] = mfma16x16x32<DT>(av, bv, acc[m][j]);
+      // (the order rd_sched counts in: the next A row, then the next substep's B reads)
+      if constexpr (j == 0 && gr + 1 < NS * MREP) rd_a(std::integral_constant<int, gr + 1>{});
+      if constexpr (ks + 1 < NS) {
+        constexpr int lo = i * 2 * NREP / RdSched::M, hi = (i + 1) * 2 * NREP / RdSched::M;
+        if constexpr (hi > lo) rd_b(std::integral_constant<int, ks + 1>{}, std::integral_constant<int, lo>{});
+        static_assert(hi - lo <= 1, "at most one B read per MFMA");
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    });
+  };
+  // the eighth wave's k-tile when the block owns its bias sum: the dY fragments against ones
+  auto bias_sum = [&]() {
+    s16x4 h[NS][2 * MREP];
+#pragma unroll
+    for (int ks = 0; ks < NS; ++ks)
+#pragma unroll
+      for (int rr = 0; rr < 2 * MREP; ++rr) h[ks][rr] = rd_tr_read_a(abase[rr >> 1], (32 * ks + 4 * (rr & 1)) * RB);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int ks = 0; ks < NS; ++ks)
+#pragma unroll
+      for (int m = 0; m < MREP; ++m)
+        accb[m] = mfma16x16x32<DT>(__builtin_bit_cast(bf16x8, __builtin_shufflevector(h[ks][2 * m], h[ks][2 * m + 1],
+                                                                                     0, 1, 2, 3, 4, 5, 6, 7)),
+                                   ones, accb[m]);
+  };
+
+  // pipeline: k-tile i in ring slot i % 3, issued two k-tiles ahead (clamped: static vmcnt)
+  int in_ = n, iy = py, ix = px0, issued = 0;  // position of the next k-tile to issue
+  auto issue_next = [&](int slot) {
+    issue(slot, in_, iy, ix);
+    if (++issued < nkt) {
+      ix += KP;
+      if (ix == p.PW) { ix = 0; if (++iy == p.PH) { iy = 0; ++in_; } }
+    }
+  };
+  // (the newest k-tile's DMAs stay in flight: 5 on waves 0 and 1, 4 on the others)
+  auto wait_barrier = [&]() {
+    if (third) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  };
+  issue_next(0);
+  issue_next(1);
+  wait_barrier();  // retires k-tile 0
+  // (one loop for the tap waves and one for the eighth: with both roles in one loop body the
+  // accumulators did not stay in place over the MFMAs)
+  auto k_loop = [&](auto tapc) {
+    int slot = 0;
+    for (int kt = 0; kt < nkt; ++kt) {
+      issue_next(slot == 0 ? 2 : slot - 1);
+      if constexpr (decltype(tapc)::value) compute();
+      else if (bias_wave && (kt0 + kt) % p.bshare == r0) bias_sum();
+      wait_barrier();  // retires k-tile kt+1, kt+2 stays in flight
+      // the fragment bases follow the ring
+      const int step = slot == 2 ? -2 * STAGE : STAGE;
+#pragma unroll
+      for (int m = 0; m < MREP; ++m) abase[m] += step;
+#pragma unroll
+      for (int j = 0; j < NREP; ++j) { bbase[j][0] += step; bbase[j][1] += step; }
+      pin_bases();
+      slot = slot == 2 ? 0 : slot + 1;
+    }
+  };
+  if (tap_wave) k_loop(std::true_type{});
+  else k_loop(std::false_type{});
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+
+  // ---- epilogue as above, in chunks of 16 dW rows (one MFMA block row of every tap wave)
+  constexpr int BN = NT * BC, LDC = BN + 4;
+  static_assert(16 * LDC * 4 <= 3 * STAGE, "a block row of the C tile fits in the LDS ring");
+  float* Cs = reinterpret_cast<float*>(lds);
+  const int amax = min(BM, p.Ca);
+  auto col_off = [&](int col) -> int {  // dW element offset of tile column col at a = 0; -1: padding
+    const int s = col / BC, b = col % BC;
+    if (b >= p.Cb) return -1;
+    return b * p.w_sb + r0 * p.w_sr + s * p.w_ss;
+  };
+  constexpr int CG = (BN + 63) / 64;
+  int coff[CG];
+#pragma unroll
+  for (int c = 0; c < CG; ++c) coff[c] = (c * 64 + lane < BN) ? col_off(c * 64 + lane) : -1;
+  const bool vec_base = p.w_sb == 1 && (p.w_sa & 3) == 0 && ((uintptr_t)p.dW & 15) == 0;
+  asm volatile("s_barrier" ::: "memory");  // (every wave's DMAs retired above: the ring is free)
+#pragma unroll
+  for (int m = 0; m < MREP; ++m) {
+    if (m > 0) __syncthreads();  // the previous chunk has been read
+    if (tap_wave) {
+#pragma unroll
+      for (int j = 0; j < NREP; ++j)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) Cs[(4 * g + reg) * LDC + wave * BC + j * 16 + l16] = acc[m][j][reg];
+    }
+    __syncthreads();
+    const int rows = min(16, amax - m * 16);
+    if (p.ksplit == 1) {
+      constexpr int CPR = BN / 4;
+      for (int idx = tid; idx < rows * CPR; idx += 512) {
+        const int row = idx / CPR, cc = 4 * (idx - row * CPR);
+        const float4 v = *reinterpret_cast<const float4*>(Cs + row * LDC + cc);
+        float* dst = p.dW + (m * 16 + row) * p.w_sa;
+        const int o0 = col_off(cc);
+        if (vec_base && o0 >= 0 && (o0 & 3) == 0 && col_off(cc + 3) == o0 + 3) {
+          float4* d4 = reinterpret_cast<float4*>(dst + o0);
+          float4 o = *d4;
+          o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w;
+          *d4 = o;
+        } else {
+          const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int oe = col_off(cc + e);
+            if (oe >= 0) dst[oe] += vv[e];
+          }
+        }
+      }
+    } else {
+      for (int row = wave; row < rows; row += 8) {
+        float* dst = p.dW + (m * 16 + row) * p.w_sa;
+#pragma unroll
+        for (int c = 0; c < CG; ++c)
+          if (coff[c] >= 0) atomicAdd(dst + coff[c], Cs[row * LDC + c * 64 + lane]);
+      }
+    }
+  }
+  if (bias_wave && l16 == 0) {  // every column of accb holds the row sum
+#pragma unroll
+    for (int m = 0; m < MREP; ++m)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int a = m * 16 + 4 * g + reg;
+        if (a >= p.Ca) continue;
+        if (p.ksplit == 1 && p.bshare == 1) p.dbias[a] += accb[m][reg];
+        else atomicAdd(p.dbias + a, accb[m][reg]);
+      }
+  }
+}
+
 // tile configs {id, BM, BC}; id = desc.algo - 6 (ids 4, 5: image mode, 32-channel b tiles;
-// id 6: row mode, 256 dY channels per block, waves 64 x (NT x 32) / 2)
+// id 6: row mode, 256 dY channels per block, waves 64 x (NT x 32) / 2; id 7: the dense
+// 80 x (7 x 80) tile, wgrad_rd_kernel)
 #define TPG_WGRAD_RH_CFGS(X) \
   X(0, 128, 64)              \
   X(1, 128, 32)              \
@@ -472,7 +837,20 @@ int wgrad_rh_tile(int cfg, int* bm, int* bc) {
 #define X(id, BM_, BC_) if (cfg == (id)) { *bm = BM_; *bc = BC_; return 0; }
   TPG_WGRAD_RH_CFGS(X)
 #undef X
+  if (cfg == 7) { *bm = 80; *bc = 80; return 0; }
   return -1;
+}
+
+static int launch_rd(const WgradRHArgs& a, hipStream_t s) {
+  const size_t lds = 3 * (64 + 72) * 256;
+  auto k1 = wgrad_rd_kernel<1>;
+  auto k2 = wgrad_rd_kernel<2>;
+  static bool once = ((void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                      (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                      true);
+  (void)once;
+  hipLaunchKernelGGL(a.dtype == 2 ? k2 : k1, dim3(a.tiles * a.ksplit), dim3(512), lds, s, a);
+  return (int)hipGetLastError();
 }
 
 template <int NR, int NT, int BM, int BC>
@@ -512,6 +890,8 @@ int launch_wgrad_rh(const WgradRHArgs& a, hipStream_t s) {
   if (a.cfg == (id)) return launch_rh_cfg<id, BM_, BC_>(a, s);
   TPG_WGRAD_RH_CFGS(X)
 #undef X
+  if (a.cfg == 7 && a.nr == 1 && a.nt == 7 && a.kw == 7 && a.Ca <= 80 && a.Cb <= 80 && a.tw == 64 && a.tiles == a.kh)
+    return launch_rd(a, s);
   return -1;
 }
 
