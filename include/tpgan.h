@@ -39,6 +39,15 @@
  *   tpg_image_metrics_u8    per-image squared error (PSNR) and SSIM of a u8 result against the u8
  *                           ground truth (build-defined, no reference code: the validation pass of
  *                           a TP-GAN training loop, as Pretrain.py:197-249 is for the landmark net)
+ *   tpg_l2_normalize        unit-length f32 embeddings of the identity extractor's features
+ *                           (torch.nn.functional.normalize; build-defined like the two below: the
+ *                           reference has no evaluation script, TP-GAN is judged on rank-1
+ *                           identification and identity-feature similarity)
+ *   tpg_cosine_topk         the k best gallery rows of every probe by cosine similarity, without
+ *                           the P x G matrix (torch.matmul + torch.topk); tpg_cosine_topk_workspace
+ *                           sizes its scratch
+ *   tpg_cosine_pairs        row-wise cosine similarity of two feature batches
+ *                           (torch.nn.functional.cosine_similarity)
  *
  * Conventions
  *   - Every tensor is described by tpg_tensor: a device pointer, a dtype and the element
@@ -522,6 +531,59 @@ int32_t tpg_denorm_u8(int32_t n, int32_t c, int32_t h, int32_t w, tpg_tensor x, 
 int64_t tpg_image_metrics_workspace(int32_t n, int32_t h, int32_t w, int32_t c);
 int32_t tpg_image_metrics_u8(int32_t n, int32_t h, int32_t w, int32_t c, const uint8_t* a, const uint8_t* b,
                              int64_t* sse, float* ssim, void* ws, size_t ws_bytes, tpg_stream_t stream);
+
+/* Identity scoring.  Rows are described by the first two strides of a tpg_tensor: element (r, e) of
+ * a logical [n][d] view is data[r * stride[0] + e * stride[1]]; stride[2] and stride[3] are ignored.
+ *   tpg_l2_normalize  x: logical [n][d], TPG_F32 / TPG_BF16 / TPG_F16, any row and element stride,
+ *                  n in 0..2^24, d in 1..4096.  out: f32 [n][dpad] contiguous, dpad = d rounded up to
+ *                  a multiple of 4 (anything else is rejected); columns d..dpad-1 are written as 0.
+ *                  Per row: ss = sum x^2 in f32 (fmaf; lane l of a 64-lane wave adds elements l,
+ *                  l + 64, ... in order, then the lanes are added by a xor butterfly: a fixed order,
+ *                  reruns are bit-identical), out = x / sqrtf(ss) (correctly rounded division).
+ *                  norm[n] (f32, may be NULL) = sqrtf(ss) as computed.
+ *                  status[n] (int32) = 1 where an element of the row is NaN or infinite, where ss
+ *                  is 0 or where ss overflowed f32; else 0.  A status-1 row is written as all zeros
+ *                  (its norm is what sqrtf gave: 0, inf or NaN).
+ *   tpg_cosine_topk  probes: f32 [P][dpad], gallery: f32 [G][dpad], both contiguous, 16-byte aligned,
+ *                  unit rows with zero pad columns as tpg_l2_normalize writes them (the scores are
+ *                  plain dot products: rows of another length give dot products, not cosines; a row
+ *                  of zeros scores 0 against everything).  P and G in 0..2^24, d in 1..4096, dpad as
+ *                  above, k in 1..8.
+ *                  skip: int32 [P] or NULL: the gallery index probe p must not match (protocols where
+ *                  the probe set is the gallery); -1, any index outside 0..G-1, or a NULL pointer
+ *                  excludes nothing.
+ *                  idx: int32 [P][k], score: f32 [P][k]: per probe the k best eligible gallery rows,
+ *                  score descending, equal scores ordered by the lower gallery index.  Slots beyond
+ *                  the number of eligible rows hold idx = -1, score = -inf.  A NaN score (a gallery or
+ *                  probe row holding NaN) is never listed.
+ *                  Arithmetic: v_mfma_f32_32x32x2_f32, i.e. per (probe, gallery row) one f32 fmaf
+ *                  chain over the dpad columns in a fixed order that depends on neither the row's
+ *                  place in a tile nor the chunking: duplicate gallery rows score bit-equal, every
+ *                  gchunk gives the same scores, reruns are bit-identical.  No atomics; partial
+ *                  lists are merged in chunk order.
+ *                  gchunk: gallery rows per block. 0 = automatic (whole tiles of 128 rows, about
+ *                  1024 blocks where the gallery allows); >= 16 forces it (tests force several chunks
+ *                  at a tiny G); 1..15 is rejected.
+ *                  ws: device scratch, 8-byte aligned, at least tpg_cosine_topk_workspace(P, G, k,
+ *                  gchunk) bytes: one (score, index) list of k entries per probe and chunk.  The
+ *                  query is positive for valid sizes (8 at least) and negative on a bad size, k or
+ *                  gchunk, or where probe tiles x chunks reaches 2^31.
+ *                  Two launches (search, merge); the similarity matrix is never stored.
+ *   tpg_cosine_pairs  a, b: logical [n][d] as for tpg_l2_normalize, each its own dtype and strides.
+ *                  cos[n] (f32) = dot / (sqrtf(|a|^2) * sqrtf(|b|^2)), the three sums in f32 in the
+ *                  fixed order above.  status[n] = 1 where either row holds a NaN or infinity, has a
+ *                  zero sum of squares or one that overflowed; cos is 0 there.  One launch, no
+ *                  workspace.
+ * Validation comes before any device work: NULL pointers (-10), sizes, k, d, dpad, gchunk (-2), dtypes
+ * (-3), alignment and workspace size (-4), each with a tpg_last_error() message. */
+int32_t tpg_l2_normalize(int32_t n, int32_t d, tpg_tensor x, float* out, int32_t dpad, float* norm, int32_t* status,
+                         tpg_stream_t stream);
+int64_t tpg_cosine_topk_workspace(int32_t P, int32_t G, int32_t k, int32_t gchunk);
+int32_t tpg_cosine_topk(int32_t P, int32_t G, int32_t d, int32_t dpad, const float* probes, const float* gallery,
+                        int32_t k, const int32_t* skip, int32_t gchunk, int32_t* idx, float* score, void* ws,
+                        size_t ws_bytes, tpg_stream_t stream);
+int32_t tpg_cosine_pairs(int32_t n, int32_t d, tpg_tensor a, tpg_tensor b, float* cos, int32_t* status,
+                         tpg_stream_t stream);
 
 /* Deterministic mode (process-wide, off by default; SURVEY.md §5 race detection): every
  * reduction runs in a fixed order — no split-K fp32 atomics in the conv forward / input

@@ -17,6 +17,16 @@ Frontalizer in bf16 on a resident batch of synthetic raw WxH photos with synthet
     the kernel has to move (HBM peak 8 TB/s, MI355X_MICROARCH.md).  Both are launch-latency
     sized at this batch; the --big line times them on 1024 faces, where the bytes dominate.
 
+--identity runs the identity-scoring leg instead (profiles/r10/identity.txt), in one process:
+
+  - tpgan_ops.cosine_topk at P = 4096 probes, D = 512, k = 5 against G = 16384 and G = 131072
+    unit rows, and torch.matmul + torch.topk on the same rows (hipBLAS plus a P x G float32 matrix
+    in memory) as the baseline: `rounds` rounds, each timing one then the other with HIP events
+    around back-to-back calls, after both are warmed up; the median round is reported with the
+    spread, the share of the 157 TF f32 matrix peak (2 P G D over the time) and the bytes of the
+    similarity matrix the fused search never writes;
+  - IdentityScorer.embed at B = 32 with the ResNet-18 back-end in bf16.
+
 Prints one JSON line per measurement; --out also writes them to a file.
 """
 import argparse
@@ -46,6 +56,62 @@ def events(fn, iters):
     return e0.elapsed_time(e1) / iters, (time.perf_counter() - t0) * 1e3 / iters
 
 
+F32_MATRIX_PEAK = 157e12  # MI355X f32-input MFMA peak, FLOP/s (MI355X_MICROARCH.md)
+
+
+def identity_leg(a, emit):
+    import FeatureExtract as FE
+    import tpgan_infer
+    import tpgan_ops
+    dev = torch.device("cuda", 0)
+    P, D, k = 4096, 512, 5
+    gen = torch.Generator(device=dev).manual_seed(0)
+    probes, _ = tpgan_ops.l2_normalize(torch.randn(P, D, generator=gen, device=dev))
+    for G, iters in ((16384, 200), (131072, 40)):
+        gallery, _ = tpgan_ops.l2_normalize(torch.randn(G, D, generator=gen, device=dev))
+
+        def fused():
+            return tpgan_ops.cosine_topk(probes, gallery, k=k)
+
+        def aten():
+            return torch.topk(torch.matmul(probes, gallery.t()), k, dim=1)
+        for _ in range(3):
+            idx, score = fused()
+            ref = aten()
+        torch.cuda.synchronize()
+        same = float((idx.long() == ref.indices).float().mean())
+        dmax = float((score - ref.values).abs().max())
+        t_f, t_a = [], []
+        for _ in range(a.rounds):  # interleaved: the two forms alternate on the same box
+            t_f.append(events(fused, iters)[0])
+            t_a.append(events(aten, iters)[0])
+        mf, ma = float(np.median(t_f)), float(np.median(t_a))
+        flop = 2.0 * P * G * D
+        emit({"op": "cosine_topk vs torch.matmul + torch.topk, f32 unit rows", "P": P, "G": G, "D": D, "k": k,
+              "rounds": a.rounds, "calls_per_round": iters,
+              "fused_ms": round(mf, 4), "fused_ms_min_max": [round(min(t_f), 4), round(max(t_f), 4)],
+              "aten_ms": round(ma, 4), "aten_ms_min_max": [round(min(t_a), 4), round(max(t_a), 4)],
+              "fused_over_aten": round(mf / ma, 4),
+              "fused_TFLOPs": round(flop / (mf * 1e-3) / 1e12, 2),
+              "fused_share_of_157TF_f32_matrix_peak": round(flop / (mf * 1e-3) / F32_MATRIX_PEAK, 4),
+              "similarity_matrix_bytes_not_written": P * G * 4,
+              "indices_equal_to_aten": round(same, 6), "max_abs_score_diff": dmax,
+              "note": "fused time is both launches (search + merge) of the whole call; aten time is the GEMM "
+                      "and the top-k over the stored P x G matrix"})
+        del gallery, ref
+    torch.manual_seed(0)
+    scorer = tpgan_infer.IdentityScorer(FE.FeatureExtractModel("resnet"), device=dev, compute_dtype=torch.bfloat16)
+    B = 32
+    faces = torch.randint(0, 256, (B, 128, 128, 3), dtype=torch.uint8, device=dev)
+    for _ in range(3):
+        scorer.embed(faces)
+    torch.cuda.synchronize()
+    ms, wall = events(lambda: scorer.embed(faces), a.iters)
+    emit({"op": "IdentityScorer.embed (u8 128x128x3 -> unit f32 [B, 512]), ResNet-18 back-end, bf16", "batch": B,
+          "ms_per_batch": round(ms, 3), "ms_per_batch_host_clock": round(wall, 3),
+          "faces_per_s": round(B / (ms * 1e-3), 1)})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -53,10 +119,24 @@ def main():
     ap.add_argument("--kiters", type=int, default=200)
     ap.add_argument("--raw", default="640x480", metavar="WxH")
     ap.add_argument("--big", type=int, default=1024, help="faces of the kernels-alone line")
+    ap.add_argument("--identity", action="store_true", help="the identity-scoring leg instead of the image path")
+    ap.add_argument("--rounds", type=int, default=5, help="interleaved rounds of the identity leg")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_infer.py needs a ROCm GPU (there is no CPU path)")
+    if a.identity:
+        lines = []
+
+        def emit_id(d):
+            lines.append(json.dumps(d))
+            print(lines[-1], flush=True)
+        identity_leg(a, emit_id)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     import D_and_G_model as DG
     import tpgan_infer
     import tpgan_ops

@@ -19,6 +19,10 @@
 // seeded sample of input sizes in 1..4096 times the outputs {1, 32, 64, 128, 256}, into heap
 // arrays of exactly out*2 and out*ksize ints (an off-by-one in ksize writes past them), and the
 // job builder and size queries with malformed arguments.
+// The identity search's host side (tpg_identity.hip) too: tpg_cosine_topk_workspace over a seeded walk
+// of (P, G, k, gchunk) up to 2^24 rows, whose size must be positive, hold at least one k-entry list
+// per probe and chunk and not shrink when P or the number of chunks grows, and every argument the
+// three launch entry points reject (which must stop them before any device work).
 // Built with `make -C tp-gan_amd asan` (planner object compiled with -fsanitize=address on
 // the host side only; the kernels are the product's) and run by tests/test_capi.py.
 // Exit status: 0 clean, 1 a consistency check failed; ASan aborts on a memory error.
@@ -302,6 +306,110 @@ static void resize_jobs() {
   free(jobs);
 }
 
+// Identity search: the chunk planner and the validation of tpg_l2_normalize / tpg_cosine_topk /
+// tpg_cosine_pairs.  Every launch call below is malformed in exactly one way; the pointers are never
+// dereferenced on the host.
+static long g_idplans = 0;
+static void identity_sweep(long iters) {
+  const int ks[] = {1, 2, 5, 8}, bad_k[] = {0, -1, 9, 2147483647}, bad_chunk[] = {1, 7, 15, -1, -2147483647 - 1};
+  const int sizes[] = {0, 1, 2, 17, 64, 127, 128, 129, 300, 1031, 4096, 16384, 131072, 1 << 20, (1 << 24) - 1, 1 << 24};
+  for (long it = 0; it < iters; ++it) {
+    const int P = rnd() % 3 ? pick(sizes, 16) : (int)(rnd() % ((1u << 24) + 1));
+    const int G = rnd() % 3 ? pick(sizes, 16) : (int)(rnd() % ((1u << 24) + 1));
+    const int k = pick(ks, 4);
+    int gchunk = rnd() % 2 ? 0 : 16 + (int)(rnd() % 5000);
+    if (rnd() % 16 == 0) gchunk = 2147483647;
+    const int64_t ws = tpg_cosine_topk_workspace(P, G, k, gchunk);
+    ++g_idplans;
+    if (ws < 0) {
+      // only a forced chunk this small on a gallery this large may be refused (2^31 blocks)
+      if (gchunk == 0 || ((int64_t)P + 127) / 128 * (((int64_t)G + gchunk - 1) / gchunk) <= 0x7fffffffLL) {
+        fprintf(stderr, "cosine_topk_workspace(%d, %d, %d, %d) = %lld: %s\n", P, G, k, gchunk, (long long)ws, tpg_last_error());
+        g_fail = 1;
+      }
+      continue;
+    }
+    int64_t least = gchunk ? (int64_t)8 * P * k * (((int64_t)G + gchunk - 1) / gchunk) : (int64_t)8 * P * k * (G > 0);
+    if (ws < 8 || ws < least) {
+      fprintf(stderr, "cosine_topk_workspace(%d, %d, %d, %d) = %lld < %lld\n", P, G, k, gchunk, (long long)ws, (long long)least);
+      g_fail = 1;
+    }
+    if (P < (1 << 24) && tpg_cosine_topk_workspace(P + 1, G, k, gchunk) < ws && tpg_cosine_topk_workspace(P + 1, G, k, gchunk) >= 0 && gchunk) {
+      fprintf(stderr, "cosine_topk_workspace shrinks from P = %d to %d (G %d k %d gchunk %d)\n", P, P + 1, G, k, gchunk);
+      g_fail = 1;
+    }
+    if (gchunk >= 32 && gchunk < 2147483647) {  // half the chunk length: at least as many chunks
+      const int64_t w2 = tpg_cosine_topk_workspace(P, G, k, gchunk / 2);
+      if (w2 >= 0 && w2 < ws) {
+        fprintf(stderr, "cosine_topk_workspace shrinks with more chunks (P %d G %d k %d gchunk %d)\n", P, G, k, gchunk);
+        g_fail = 1;
+      }
+    }
+  }
+  int accepted = 0;
+  float* f = (float*)0x10000;
+  int32_t* i32 = (int32_t*)0x20000;
+  void* ws = (void*)0x30000;
+  tpg_tensor t, nul;
+  memset(&t, 0, sizeof(t));
+  memset(&nul, 0, sizeof(nul));
+  t.data = f; t.dtype = TPG_F32; t.stride[0] = 512; t.stride[1] = 1;
+  nul.stride[0] = 512; nul.stride[1] = 1;
+  tpg_tensor badt = t;
+  badt.dtype = 7;
+  for (int k : bad_k) {
+    accepted += tpg_cosine_topk_workspace(4, 100, k, 0) >= 0;
+    accepted += tpg_cosine_topk(4, 100, 512, 512, f, f, k, nullptr, 0, i32, f, ws, 1 << 20, nullptr) == 0;
+  }
+  for (int c : bad_chunk) {
+    accepted += tpg_cosine_topk_workspace(4, 100, 1, c) >= 0;
+    accepted += tpg_cosine_topk(4, 100, 512, 512, f, f, 1, nullptr, c, i32, f, ws, 1 << 20, nullptr) == 0;
+  }
+  const int bad_n[] = {-1, (1 << 24) + 1, -2147483647 - 1, 2147483647}, bad_d[] = {0, -1, 4097, 2147483647, -2147483647 - 1};
+  for (int n : bad_n) {
+    accepted += tpg_cosine_topk_workspace(n, 100, 1, 0) >= 0;
+    accepted += tpg_cosine_topk_workspace(4, n, 1, 0) >= 0;
+    accepted += tpg_cosine_topk(n, 100, 512, 512, f, f, 1, nullptr, 0, i32, f, ws, 1 << 20, nullptr) == 0;
+    accepted += tpg_cosine_topk(4, n, 512, 512, f, f, 1, nullptr, 0, i32, f, ws, 1 << 20, nullptr) == 0;
+    accepted += tpg_l2_normalize(n, 512, t, f, 512, f, i32, nullptr) == 0;
+    accepted += tpg_cosine_pairs(n, 512, t, t, f, i32, nullptr) == 0;
+  }
+  for (int d : bad_d) {
+    accepted += tpg_cosine_topk(4, 100, d, 512, f, f, 1, nullptr, 0, i32, f, ws, 1 << 20, nullptr) == 0;
+    accepted += tpg_l2_normalize(4, d, t, f, 512, f, i32, nullptr) == 0;
+    accepted += tpg_cosine_pairs(4, d, t, t, f, i32, nullptr) == 0;
+  }
+  // dpad that is not d rounded up to a multiple of 4
+  accepted += tpg_l2_normalize(4, 515, t, f, 515, f, i32, nullptr) == 0;
+  accepted += tpg_l2_normalize(4, 515, t, f, 520, f, i32, nullptr) == 0;
+  accepted += tpg_l2_normalize(4, 512, t, f, 516, f, i32, nullptr) == 0;
+  accepted += tpg_cosine_topk(4, 100, 515, 515, f, f, 1, nullptr, 0, i32, f, ws, 1 << 20, nullptr) == 0;
+  accepted += tpg_cosine_topk(4, 100, 3, 8, f, f, 1, nullptr, 0, i32, f, ws, 1 << 20, nullptr) == 0;
+  // NULL pointers, bad dtypes, misaligned rows, a short workspace
+  accepted += tpg_l2_normalize(4, 512, nul, f, 512, f, i32, nullptr) == 0;
+  accepted += tpg_l2_normalize(4, 512, t, nullptr, 512, f, i32, nullptr) == 0;
+  accepted += tpg_l2_normalize(4, 512, t, f, 512, f, nullptr, nullptr) == 0;
+  accepted += tpg_l2_normalize(4, 512, badt, f, 512, f, i32, nullptr) == 0;
+  accepted += tpg_cosine_pairs(4, 512, nul, t, f, i32, nullptr) == 0;
+  accepted += tpg_cosine_pairs(4, 512, t, nul, f, i32, nullptr) == 0;
+  accepted += tpg_cosine_pairs(4, 512, t, t, nullptr, i32, nullptr) == 0;
+  accepted += tpg_cosine_pairs(4, 512, t, t, f, nullptr, nullptr) == 0;
+  accepted += tpg_cosine_pairs(4, 512, t, badt, f, i32, nullptr) == 0;
+  accepted += tpg_cosine_topk(4, 100, 512, 512, nullptr, f, 1, nullptr, 0, i32, f, ws, 1 << 20, nullptr) == 0;
+  accepted += tpg_cosine_topk(4, 100, 512, 512, f, nullptr, 1, nullptr, 0, i32, f, ws, 1 << 20, nullptr) == 0;
+  accepted += tpg_cosine_topk(4, 100, 512, 512, f, f, 1, nullptr, 0, nullptr, f, ws, 1 << 20, nullptr) == 0;
+  accepted += tpg_cosine_topk(4, 100, 512, 512, f, f, 1, nullptr, 0, i32, nullptr, ws, 1 << 20, nullptr) == 0;
+  accepted += tpg_cosine_topk(4, 100, 512, 512, f, f, 1, nullptr, 0, i32, f, nullptr, 1 << 20, nullptr) == 0;
+  accepted += tpg_cosine_topk(4, 100, 512, 512, f + 1, f, 1, nullptr, 0, i32, f, ws, 1 << 20, nullptr) == 0;
+  accepted += tpg_cosine_topk(4, 100, 512, 512, f, f + 2, 1, nullptr, 0, i32, f, ws, 1 << 20, nullptr) == 0;
+  accepted += tpg_cosine_topk(4, 100, 512, 512, f, f, 1, nullptr, 0, i32, f, (char*)ws + 4, 1 << 20, nullptr) == 0;
+  const int64_t need = tpg_cosine_topk_workspace(4, 100, 8, 16);
+  accepted += tpg_cosine_topk(4, 100, 512, 512, f, f, 8, nullptr, 16, i32, f, ws, (size_t)need - 1, nullptr) == 0;
+  accepted += tpg_cosine_topk(4, 100, 512, 512, f, f, 8, nullptr, 16, i32, f, ws, 0, nullptr) == 0;
+  if (need != 8 * 4 * 8 * 7) { fprintf(stderr, "cosine_topk_workspace(4, 100, 8, 16) = %lld\n", (long long)need); g_fail = 1; }
+  if (accepted) { fprintf(stderr, "identity: %d malformed calls accepted\n", accepted); g_fail = 1; }
+}
+
 static tpg_conv_desc conv(int n, int ci, int h, int w, int co, int k, int s, int p, int dt, bool T = false,
                           int op_pad = 0, int pm = TPG_PAD_ZERO) {
   tpg_conv_desc d;
@@ -414,7 +522,9 @@ int main(int argc, char** argv) {
     for (int i = 0; i < 24; ++i) resize_table(1 + (int)(rnd() % 4096), out);
   }
   resize_jobs();
+  identity_sweep(iters < 2000 ? iters : 2000);
   printf("planner_asan: %ld valid, %ld rejected descriptors, %ld pack jobs, %ld wgrad plans, %ld data plans, "
-         "%ld resize tables, %s\n", g_valid, g_rejected, g_jobs, g_plans, g_dplans, g_tables, g_fail ? "FAILED" : "ok");
+         "%ld resize tables, %ld top-k plans, %s\n", g_valid, g_rejected, g_jobs, g_plans, g_dplans, g_tables, g_idplans,
+         g_fail ? "FAILED" : "ok");
   return g_fail;
 }

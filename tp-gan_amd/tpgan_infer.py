@@ -4,12 +4,22 @@ uint8 frontal faces, and PSNR / SSIM against the ground-truth frontal view.
     fz = Frontalizer.from_checkpoint("ckpt", epoch=3)        # or Frontalizer(G)
     u8 = fz(imgs, lm68)                                      # uint8 [B, 128, 128, 3]
     r = fz.evaluate(imgs, lm68, frontal)                     # fake_u8, sse, psnr, ssim
+    ids = IdentityScorer(FeatureExtractModel("resnet"))      # a trained identity network
+    r = fz.evaluate(imgs, lm68, frontal, identity=ids)       # ... and id_cos
+    ids.enroll(gallery_u8, labels)                           # frontal views, one label each
+    hit = ids.identify(fz(imgs, lm68), k=5)                  # idx, score, label [B, 5]
+    cmc = ids.cmc(true_labels, hit)                          # rank-1 .. rank-5 rates
 
 The data path is FaceBatcher.from_raw (Pillow-exact LANCZOS, landmark crops, [-1, 1]), the
 model is the product's Generator frozen in eval mode, the way back to pixels is
 tpgan_ops.denorm_u8 and the metrics are tpgan_ops.image_metrics: everything between the
 uploaded photos and the returned tensors stays on the device.  The frozen weights' bf16 / fp16
 images are packed once (tpgan_ops._FrozenPack) and again only after load_state_dict.
+
+TP-GAN is judged on identity, not pixels: IdentityScorer turns u8 faces into unit-length
+embeddings of a frozen FeatureExtract.FeatureExtractModel (tpgan_ops.l2_normalize), keeps a
+device-resident gallery of them and finds each probe's best matches with tpgan_ops.cosine_topk,
+which never builds the probes x gallery similarity matrix.
 """
 import os
 import re
@@ -190,10 +200,14 @@ class Frontalizer:
             out[s:e] = self._forward_u8(fb.from_raw(imgs[s:e], lm68[s:e]), z[s:e])
         return out
 
-    def evaluate(self, imgs, lm68, frontal, z=None):
+    def evaluate(self, imgs, lm68, frontal, z=None, identity=None):
         """Frontalise and score against the ground-truth frontal view (uint8 [B, 128, 128, 3] on the
         device, or a list of raw photos, resized like the inputs) -> {"fake_u8", "sse" int64 [B],
-        "psnr" float64 [B] (inf where sse is 0), "ssim" float32 [B]}."""
+        "psnr" float64 [B] (inf where sse is 0), "ssim" float32 [B]}.  With identity=an
+        IdentityScorer the dict also holds "id_cos" float32 [B]: the cosine similarity of the
+        identity embeddings of the frontalised face and of the true frontal view."""
+        if identity is not None and not isinstance(identity, IdentityScorer):
+            raise ValueError("identity must be an IdentityScorer or None, got %s" % type(identity).__name__)
         fake = self(imgs, lm68, z)
         if isinstance(frontal, torch.Tensor) and frontal.dim() == 4 and tuple(frontal.shape[1:]) == (128, 128, 3):
             if frontal.dtype != torch.uint8:
@@ -204,10 +218,166 @@ class Frontalizer:
         if real.shape != fake.shape:
             raise ValueError("frontal holds %d faces, imgs %d" % (real.shape[0], fake.shape[0]))
         sse, ssim = tpgan_ops.image_metrics(fake, real)
-        return {"fake_u8": fake, "sse": sse, "psnr": psnr_from_sse(sse, fake.shape[1:]), "ssim": ssim}
+        out = {"fake_u8": fake, "sse": sse, "psnr": psnr_from_sse(sse, fake.shape[1:]), "ssim": ssim}
+        if identity is not None:
+            out["id_cos"] = tpgan_ops.cosine_pairs(identity.embed(fake), identity.embed(real))
+        return out
 
 
 def psnr_from_sse(sse, hwc):
     """10 * log10(255^2 * H * W * C / sse) in float64 on sse's device (inf where sse is 0)."""
     n = float(255 * 255) * float(hwc[0]) * float(hwc[1]) * float(hwc[2])
     return 10.0 * torch.log10(n / sse.to(torch.float64))
+
+
+class IdentityScorer:
+    """Identity embeddings, a gallery of them and rank-k identification, all on the device.
+
+    extractor       a FeatureExtract.FeatureExtractModel ('resnet', 'resnet50' or 'mobilenetv2').
+                    It is moved to `device`, frozen and put in eval mode; the 16-bit images of
+                    its weights are packed once (tpgan_ops._FrozenPack), BatchNorm folded once.
+    compute_dtype   torch.bfloat16 (default), torch.float16 or torch.float32: the extractor's
+                    arithmetic.  Embeddings, similarities and the search are float32 throughout.
+    max_batch       faces per extractor pass.
+
+    An embedding is the extractor's last identity feature (pooled over the map where the
+    back-end returns a map: MobileNetV2), divided by its norm.
+    """
+
+    def __init__(self, extractor, device="cuda", compute_dtype=torch.bfloat16, max_batch=32):
+        if compute_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError("compute_dtype must be float32, bfloat16 or float16, got %s" % compute_dtype)
+        if int(max_batch) < 1:
+            raise ValueError("max_batch must be >= 1, got %s" % max_batch)
+        if not hasattr(extractor, "extract_features"):
+            raise ValueError("extractor must be a FeatureExtractModel (extract_features), got %s"
+                             % type(extractor).__name__)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.compute_dtype = compute_dtype
+        self.max_batch = int(max_batch)
+        self.extractor = extractor.to(self.device).eval()
+        for p in self.extractor.parameters():
+            p.requires_grad_(False)
+            p._tpg_flat = tpgan_ops._FrozenPack()
+        self._fb = None
+        self.clear()
+
+    # ---- embeddings
+    def _features(self, faces_u8):
+        if self._fb is None:
+            self._fb = FaceBatcher(self.device, dtype=torch.float32, check=False)
+        with torch.no_grad(), torch.cuda.device(self.device), tpgan_ops.compute_dtype(self.compute_dtype):
+            f = self.extractor.extract_features(self._fb.normalize(faces_u8))[-1]
+            if f.dim() == 4 and (f.shape[2] != 1 or f.shape[3] != 1):
+                f = tpgan_ops.global_avgpool(f)
+            return f.reshape(f.shape[0], -1)
+
+    def embed(self, faces_u8):
+        """uint8 [B, S, S, 3] faces on the device -> unit-length float32 [B, D] embeddings.  A face
+        whose feature holds NaN or infinity, or is all zero, raises ValueError naming it."""
+        if not isinstance(faces_u8, torch.Tensor) or faces_u8.dtype != torch.uint8 or faces_u8.dim() != 4 \
+                or faces_u8.shape[-1] != 3:
+            raise ValueError("faces_u8 must be a uint8 [B, S, S, 3] tensor")
+        if faces_u8.device != self.device:
+            raise ValueError("faces_u8 must be on %s, got %s" % (self.device, faces_u8.device))
+        faces_u8 = faces_u8.contiguous()
+        B = faces_u8.shape[0]
+        if B == 0:
+            raise ValueError("faces_u8 holds no faces")
+        if B <= self.max_batch:
+            feats = self._features(faces_u8)
+        else:
+            feats = torch.cat([self._features(faces_u8[s:s + self.max_batch]) for s in range(0, B, self.max_batch)])
+        unit, _, status = tpgan_ops.l2_normalize(feats, check=False)
+        bad = torch.nonzero(status != 0).flatten().tolist()
+        if bad:
+            raise ValueError("embed: the identity feature of face(s) %s holds NaN or infinity, or is zero" % bad)
+        return unit
+
+    def _embeddings(self, x, what):
+        if isinstance(x, torch.Tensor) and x.dtype == torch.uint8:
+            return self.embed(x)
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or x.device != self.device:
+            raise ValueError("%s must be uint8 [B, S, S, 3] faces or float32 [B, D] embeddings on %s"
+                             % (what, self.device))
+        return x
+
+    # ---- gallery
+    def clear(self):
+        """Empty the gallery."""
+        self._gal = None     # float32 [capacity, dpad], pad columns zero
+        self._labels = None  # int64 [capacity]
+        self._dim = 0
+        self.size = 0
+
+    @property
+    def gallery(self):
+        """The enrolled embeddings, float32 [size, D] (a view of the gallery buffer)."""
+        if self._gal is None:
+            raise ValueError("the gallery is empty")
+        return tpgan_ops._zero_padded(self._gal[:self.size], self._dim)
+
+    @property
+    def labels(self):
+        if self._gal is None:
+            raise ValueError("the gallery is empty")
+        return self._labels[:self.size]
+
+    def enroll(self, faces_u8, labels):
+        """Append faces (or ready embeddings) and their integer labels to the gallery; returns the
+        gallery indices they were given, int64 [B]."""
+        emb = self._embeddings(faces_u8, "faces_u8")
+        B, D = emb.shape
+        labels = torch.as_tensor(labels)
+        if labels.dim() != 1 or labels.shape[0] != B or labels.is_floating_point() or labels.dtype == torch.bool:
+            raise ValueError("labels must be %d integers" % B)
+        labels = labels.to(self.device, torch.int64)
+        if self._gal is not None and D != self._dim:
+            raise ValueError("embeddings have %d columns, the gallery %d" % (D, self._dim))
+        dpad = (D + 3) // 4 * 4
+        need = self.size + B
+        if self._gal is None or need > self._gal.shape[0]:
+            cap = max(need, 2 * (self._gal.shape[0] if self._gal is not None else 0), 256)
+            gal = torch.zeros(cap, dpad, dtype=torch.float32, device=self.device)
+            lab = torch.full((cap,), -1, dtype=torch.int64, device=self.device)
+            if self._gal is not None:
+                gal[:self.size] = self._gal[:self.size]
+                lab[:self.size] = self._labels[:self.size]
+            self._gal, self._labels, self._dim = gal, lab, D
+        self._gal[self.size:need, :D] = emb
+        self._labels[self.size:need] = labels
+        first, self.size = self.size, need
+        return torch.arange(first, need, dtype=torch.int64, device=self.device)
+
+    # ---- identification
+    def identify(self, faces_u8, k=1, skip=None):
+        """The k best gallery matches of every probe (uint8 faces or float32 [B, D] embeddings) ->
+        {"idx" int32 [B, k], "score" float32 [B, k], "label" int64 [B, k]}: cosine similarity
+        descending, equal scores by the lower gallery index; idx and label are -1 and score -inf
+        past the number of eligible gallery rows.  skip: int32 [B], the gallery index each probe
+        must not match (the probe's own enrolment), -1 for none."""
+        if self._gal is None:
+            raise ValueError("the gallery is empty: enroll() first")
+        emb = self._embeddings(faces_u8, "faces_u8")
+        if emb.shape[1] != self._dim:
+            raise ValueError("embeddings have %d columns, the gallery %d" % (emb.shape[1], self._dim))
+        if skip is not None:
+            skip = torch.as_tensor(skip).to(self.device, torch.int32)
+        idx, score = tpgan_ops.cosine_topk(emb, self.gallery, k=k, skip=skip)
+        label = torch.where(idx >= 0, self.labels[idx.clamp(min=0).long()], torch.full_like(idx, -1, dtype=torch.int64))
+        return {"idx": idx, "score": score, "label": label}
+
+    @staticmethod
+    def cmc(probe_labels, result):
+        """Cumulative match characteristic, float64 [k] on the result's device: entry r is the
+        share of probes whose own label is among their r + 1 best matches (entry 0 is rank-1)."""
+        label = result["label"]
+        probe_labels = torch.as_tensor(probe_labels).to(label.device, torch.int64)
+        if probe_labels.dim() != 1 or probe_labels.shape[0] != label.shape[0]:
+            raise ValueError("probe_labels must hold %d labels" % label.shape[0])
+        if label.shape[0] == 0:
+            raise ValueError("no probes")
+        hit = (label == probe_labels[:, None]) & (result["idx"] >= 0)
+        return (hit.cumsum(1) > 0).to(torch.float64).mean(0)

@@ -155,6 +155,15 @@ EXPORTS = {
     "tpg_image_metrics_workspace": (ctypes.c_int64, [ctypes.c_int32] * 4),
     "tpg_image_metrics_u8": (ctypes.c_int32, [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 5 +
                              [ctypes.c_size_t, ctypes.c_void_p]),
+    "tpg_l2_normalize": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, TpgTensor, ctypes.c_void_p, ctypes.c_int32,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "tpg_cosine_topk_workspace": (ctypes.c_int64, [ctypes.c_int32] * 4),
+    "tpg_cosine_topk": (ctypes.c_int32, [ctypes.c_int32] * 4 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                                                 ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                                 ctypes.c_void_p]),
+    "tpg_cosine_pairs": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, TpgTensor, TpgTensor, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p]),
     "tpg_loss_workspace": (ctypes.c_size_t, []),
     "tpg_image_losses_fwd": (ctypes.c_int32, [ctypes.c_int32] * 4 + [TpgTensor, TpgTensor] + [ctypes.c_float] * 3 +
                              [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),

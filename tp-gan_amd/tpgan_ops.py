@@ -2194,3 +2194,154 @@ def image_metrics(a_u8, b_u8, ssim=True):
             check(lib.tpg_image_metrics_u8(n, h, w, c, a.data_ptr(), b.data_ptr(), sse.data_ptr(),
                                            sim.data_ptr() if ssim else None, ws.data_ptr(), ws.numel() * 8, stream_ptr()))
     return sse, sim
+
+
+# ---- identity scoring (tpg_identity.hip): unit-length embeddings, cosine top-k against a gallery
+# without the P x G similarity matrix, pairwise cosine.  None is differentiable.
+_ID_WS = {}
+_check_rc = check  # (l2_normalize and cosine_pairs take a `check` flag of their own)
+
+
+def _identity_ws(device, nbytes):
+    """The top-k search's partial-list scratch (one per device, grown on demand; every launch is on
+    the caller's current stream, in order)."""
+    ws = _ID_WS.get(device)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = _ID_WS[device] = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+    return ws
+
+
+def _rows_arg(fn, name, t):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ValueError("%s: %s must be a 2-D [n, d] tensor" % (fn, name))
+    if t.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError("%s: %s must be float32, bfloat16 or float16, got %s" % (fn, name, t.dtype))
+    if not 1 <= t.shape[1] <= 4096:
+        raise ValueError("%s: %s must have 1..4096 columns, got %d" % (fn, name, t.shape[1]))
+    if not t.is_cuda:
+        raise ValueError("%s: %s must be a device tensor, got a %s tensor" % (fn, name, t.device))
+    return t.detach()
+
+
+def _raise_bad_rows(fn, status, what):
+    bad = torch.nonzero(status != 0).flatten().tolist()
+    if bad:
+        raise ValueError("%s: row(s) %s %s" % (fn, bad, what))
+
+
+def _zero_padded(buf, d):
+    """The [n, d] view of a [n, dpad] buffer whose pad columns are zero, marked so that cosine_topk
+    takes the buffer as it is (a slice or copy of the view loses the mark and is re-padded)."""
+    v = buf[:, :d]
+    v._tpg_zero_pad = True
+    return v
+
+
+def l2_normalize(x, check=True):
+    """(unit, norm): the rows of a float32 / bfloat16 / float16 [n, d] device tensor of any strides
+    (d in 1..4096) divided by their Euclidean norm, as float32 [n, d] -- a view of a [n, dpad]
+    buffer, dpad = d rounded up to a multiple of 4, with zero pad columns, which cosine_topk takes
+    without a copy -- and the norms, float32 [n].  Sum of squares in float32 in a fixed order.  A
+    row holding NaN or infinity, or of norm 0, comes back as zeros; with check=True it raises
+    ValueError naming the rows (one device-to-host read), with check=False the third value
+    returned is the int32 [n] status instead."""
+    x = _rows_arg("l2_normalize", "x", x)
+    n, d = x.shape
+    dpad = (d + 3) // 4 * 4
+    lib = load()
+    with torch.no_grad(), torch.cuda.device(x.device):
+        out = torch.empty(n, dpad, dtype=torch.float32, device=x.device)
+        norm = torch.empty(n, dtype=torch.float32, device=x.device)
+        status = torch.empty(n, dtype=torch.int32, device=x.device)
+        if n:
+            _check_rc(lib.tpg_l2_normalize(n, d, tt(x), out.data_ptr(), dpad, norm.data_ptr(), status.data_ptr(),
+                                           stream_ptr()))
+    unit = _zero_padded(out, d)
+    if check:
+        _raise_bad_rows("l2_normalize", status, "hold NaN or infinity, or have norm 0")
+        return unit, norm
+    return unit, norm, status
+
+
+def _unit_rows(fn, name, t):
+    """A float32 [n, d] tensor -> (contiguous [n, dpad] buffer with zero pad columns, d)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+        raise ValueError("%s: %s must be a float32 [n, d] tensor of unit rows (l2_normalize)" % (fn, name))
+    if not t.is_cuda:
+        raise ValueError("%s: %s must be a device tensor, got a %s tensor" % (fn, name, t.device))
+    n, d = t.shape
+    if not 1 <= d <= 4096:
+        raise ValueError("%s: %s must have 1..4096 columns, got %d" % (fn, name, d))
+    dpad = (d + 3) // 4 * 4
+    if getattr(t, "_tpg_zero_pad", False) and t.stride() == (dpad, 1) and t.data_ptr() % 16 == 0:
+        return t.detach().as_strided((n, dpad), (dpad, 1)), d  # the rows with their pad columns
+    t = t.detach()
+    if d == dpad and t.is_contiguous() and t.data_ptr() % 16 == 0:
+        return t, d
+    buf = torch.zeros(n, dpad, dtype=torch.float32, device=t.device)  # any other layout: one padded copy
+    buf[:, :d].copy_(t)
+    return buf, d
+
+
+def cosine_topk(probes, gallery, k=1, skip=None, gchunk=0):
+    """(idx int32 [P, k], score float32 [P, k]): for every row of `probes` the k (1..8) rows of
+    `gallery` with the largest dot product -- the cosine similarity for unit rows, which is what
+    l2_normalize returns -- score descending, equal scores by the lower gallery index, slots past
+    the number of eligible rows -1 / -inf.  skip: int32 [P] gallery index each probe must not match
+    (-1: none).  Exact float32 MFMA; the P x G similarity matrix is never stored, reruns are
+    bit-identical, and the result does not depend on gchunk (gallery rows per block; 0 = planned,
+    >= 16 forces it).  Runs on the current stream; legal inside a graph capture once the workspace
+    has been sized by an earlier call of at least this size."""
+    pb, d = _unit_rows("cosine_topk", "probes", probes)
+    gb, dg = _unit_rows("cosine_topk", "gallery", gallery)
+    if d != dg or pb.device != gb.device:
+        raise ValueError("cosine_topk: probes [%d, %d] on %s and gallery [%d, %d] on %s do not match" %
+                         (pb.shape[0], d, pb.device, gb.shape[0], dg, gb.device))
+    k, gchunk = int(k), int(gchunk)
+    if not 1 <= k <= 8:
+        raise ValueError("cosine_topk: k must be in 1..8, got %d" % k)
+    if gchunk < 0 or 1 <= gchunk <= 15:
+        raise ValueError("cosine_topk: gchunk must be 0 or >= 16, got %d" % gchunk)
+    P, G = pb.shape[0], gb.shape[0]
+    if skip is not None:
+        if not isinstance(skip, torch.Tensor) or skip.dtype != torch.int32 or tuple(skip.shape) != (P,) \
+                or skip.device != pb.device:
+            raise ValueError("cosine_topk: skip must be an int32 [%d] tensor on %s" % (P, pb.device))
+        skip = skip.contiguous()
+    lib = load()
+    with torch.no_grad(), torch.cuda.device(pb.device):
+        idx = torch.empty(P, k, dtype=torch.int32, device=pb.device)
+        score = torch.empty(P, k, dtype=torch.float32, device=pb.device)
+        if P:
+            nb = lib.tpg_cosine_topk_workspace(P, G, k, gchunk)
+            if nb < 0:
+                check(int(nb))
+            ws = _identity_ws(pb.device, nb)
+            check(lib.tpg_cosine_topk(P, G, d, pb.shape[1], pb.data_ptr(), gb.data_ptr() if G else None, k,
+                                      skip.data_ptr() if skip is not None else None, gchunk, idx.data_ptr(),
+                                      score.data_ptr(), ws.data_ptr(), ws.numel() * 8, stream_ptr()))
+    return idx, score
+
+
+def cosine_pairs(a, b, check=True):
+    """float32 [n]: the cosine similarity of row i of `a` and row i of `b` (float32 / bfloat16 /
+    float16 [n, d] device tensors, each of any strides and its own dtype), dot / (|a| |b|) with the
+    three sums in float32 in a fixed order.  A pair with a NaN, an infinity or a zero row gives 0;
+    with check=True it raises ValueError naming the rows, with check=False the int32 [n] status is
+    returned as a second value."""
+    a = _rows_arg("cosine_pairs", "a", a)
+    b = _rows_arg("cosine_pairs", "b", b)
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError("cosine_pairs: a %s on %s and b %s on %s must match" %
+                         (tuple(a.shape), a.device, tuple(b.shape), b.device))
+    n, d = a.shape
+    lib = load()
+    with torch.no_grad(), torch.cuda.device(a.device):
+        cos = torch.empty(n, dtype=torch.float32, device=a.device)
+        status = torch.empty(n, dtype=torch.int32, device=a.device)
+        if n:
+            _check_rc(lib.tpg_cosine_pairs(n, d, tt(a), tt(b), cos.data_ptr(), status.data_ptr(), stream_ptr()))
+    if check:
+        _raise_bad_rows("cosine_pairs", status, "hold NaN or infinity, or have norm 0")
+        return cos
+    return cos, status
