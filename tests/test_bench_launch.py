@@ -71,8 +71,10 @@ def test_gpus_mismatch_exits_nonzero():
 
 def test_gpus_launches_ranks_and_nccl_needs_a_device_each():
     # no launcher in front: bench.py starts 2 ranks under torch.distributed.run; with nccl each
-    # rank refuses to share a device (this container has none), and the parent returns non-zero
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--no-cpu-baseline"], cwd=REPO, env=_env(),
+    # rank refuses to share a device (the ranks are shown none, also on a host that has one), and
+    # the parent returns non-zero
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--no-cpu-baseline"], cwd=REPO,
+                       env=_env(HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES=""),
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0
     assert "2 ranks on this node but 0 visible GPU(s)" in r.stderr, r.stderr[-3000:]

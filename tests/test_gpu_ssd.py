@@ -101,3 +101,173 @@ def test_ssd_decode_vs_oracle(gpu, seed, B, n, top_k, nms):
         assert len(got[b]) == len(want), (b, len(got[b]), len(want))
         for (c, s, p), (wc, ws, wp) in zip(got[b], want):
             assert c == wc and float(s) == pytest.approx(ws, rel=1e-5) and [float(v) for v in p] == pytest.approx(wp)
+
+
+# ---- lattice inputs (tests/test_multitask.py: LATTICE_CASES and the condition they satisfy) --------
+# The reference is the CPU tensor form in float64 on the same fp32 values; on the lattice every
+# distance comparison is exact in fp32, so labels and the background selection are demanded exact,
+# ties included.  Bounds as test_ssd_loss_and_grad_vs_tensor_form: loss 2e-5, gradients rtol 1e-4
+# atol 1e-7 (fp32 sums of up to 4096 terms and expf / logf against float64).
+# measured on the MI355X over the eleven cases -- loss <= 7.3e-8 relative; the largest
+# |got - ref| / (1e-7 + 1e-4 |ref|) of a gradient element (1 is the bound): locations 2.2e-3, logits 2.8e-3
+from test_multitask import IMAGE, LATTICE_CASES, lattice_inputs, lattice_stats  # noqa: E402
+
+
+@pytest.mark.parametrize("name,ratio_nb", [(k, nb) for k, c in LATTICE_CASES.items() for nb, _ in c["nb"]])
+def test_ssd_lattice_loss_and_grad_vs_fp64(gpu, name, ratio_nb):
+    """(B, n) = (2, 257): n2 = 512 with 255 padding keys; (1, 4096): the largest n, the largest
+    dynamic-LDS request, truth outside the image; (2, 4095): one padding key, C = 7 (class stride);
+    (3, 40) and (1, 12): fewer anchors than threads.  ratio_nb picks the background path: all of
+    them, the draw of the cap smallest keys, cap == 0 (no background term: the tensor form's
+    nsel == 0 branch, which the kernel matches through v[9] == 0)."""
+    import MobileNetV2 as M
+    import tpgan_ops
+    c = LATTICE_CASES[name]
+    pred, cls, true = lattice_inputs(name)
+    B, n, ratio = c["B"], c["n"], c["ratio"]
+    m = M.MultiTaskLoss(distance_threshold_ratio=ratio, ratio_non_background=ratio_nb)
+    pc, cc = pred.double().requires_grad_(True), cls.double().requires_grad_(True)
+    torch.manual_seed(7)
+    ref = m(pc, cc, true.double(), IMAGE)  # (its background keys: torch.rand(B, n) after the seed)
+    ref.backward()
+    torch.manual_seed(7)
+    keys = torch.rand(B, n)
+    ph, ch = pred.to(gpu).requires_grad_(True), cls.to(gpu).requires_grad_(True)
+    total, labels, sel, terms = tpgan_ops._SsdLoss.apply(ph, ch, true.to(gpu), keys.to(gpu), float(IMAGE[1]),
+                                                         float(IMAGE[0]), int(ratio * n), ratio_nb, m.alpha, m.beta)
+    total.backward()
+    torch.cuda.synchronize()
+    st = lattice_stats(pred, true, ratio)
+    assert torch.equal(labels.cpu().long(), st["labels"])
+    bg = st["labels"] == -1
+    nbg = bg.sum(dim=1, keepdim=True)
+    cap = ((n - nbg).double() * ratio_nb).floor().long()
+    rank = torch.where(bg, keys, torch.full_like(keys, 2.0)).argsort(dim=1, stable=True).argsort(dim=1)
+    assert torch.equal(sel.cpu().bool(), bg & ((nbg <= cap) | (rank < cap)))
+    gl, gc = ph.grad.cpu().double(), ch.grad.cpu().double()
+    print("ssd lattice %s nb=%s: loss %.2e loc %.2e cls %.2e" % (
+        name, ratio_nb, abs(float(total) - float(ref)) / abs(float(ref)),
+        float(((gl - pc.grad).abs() / (1e-7 + 1e-4 * pc.grad.abs())).max()),
+        float(((gc - cc.grad).abs() / (1e-7 + 1e-4 * cc.grad.abs())).max())))
+    assert float(total) == pytest.approx(float(ref), rel=2e-5)
+    assert torch.allclose(gl, pc.grad, rtol=1e-4, atol=1e-7)
+    assert torch.allclose(gc, cc.grad, rtol=1e-4, atol=1e-7)
+    # the clamp: no gradient on an axis whose coordinate lies outside [0, size]; on 0 or size exactly
+    # it passes (inclusive, as torch.clamp), with the reference's non-zero value
+    assert bool((gl[st["outside"]] == 0).all()) and bool((pc.grad[st["outside"]] == 0).all())
+    assert bool((gl[st["edge"]] != 0).all()) and bool((pc.grad[st["edge"]] != 0).all())
+    for what in c["plants"]:
+        assert bool(st[what].any())
+
+
+# ---- decode: ties, the NMS boundary, top_k up to 64, every slot written -------------------------
+def _decode_vs_oracle(gpu, pred, cls, conf, top_k, nms):
+    import MobileNetV2 as M
+    got = M.MultiTaskDecoder(confidence_threshold=conf, top_k=top_k, nms_distance_threshold=nms)(pred.to(gpu),
+                                                                                                  cls.to(gpu))
+    wants = []
+    for b in range(pred.shape[0]):
+        want = O.decode(O.as_lists(pred[b].double()), O.as_lists(cls[b].double()), confidence_threshold=conf,
+                        top_k=top_k, nms_distance_threshold=nms)
+        assert len(got[b]) == len(want), (b, len(got[b]), len(want))
+        for (c, s, p), (wc, ws, wp) in zip(got[b], want):
+            assert c == wc and float(s) == pytest.approx(ws, rel=1e-5) and [float(v) for v in p] == wp
+        wants.append(want)
+    return wants
+
+
+def _lattice_points(seed, B, n, C):
+    g = torch.Generator().manual_seed(seed)
+    pred = (16 * torch.randint(-8, 49, (B, n, 2), generator=g)).float()
+    cls = torch.randn(B, n, C, generator=g) * 3
+    return pred, cls
+
+
+@pytest.mark.parametrize("seed,B,n,C,conf,top_k", [
+    (31, 2, 1000, 5, 0.2, 64),   # hundreds of survivors per class: all 64 slots kept, the 65th dropped
+    (32, 1, 4096, 5, 0.97, 64),  # the largest n: 48 KiB of dynamic LDS, n2 == n (no padding key)
+    (33, 2, 257, 7, 0.3, 16),    # C = 7: the class stride, seven blocks per image
+    (34, 3, 1, 5, 0.1, 3),       # one anchor: n2 = 1, the sort loops do not run
+])
+def test_ssd_decode_lattice_vs_oracle(gpu, seed, B, n, C, conf, top_k):
+    """Lattice points 16 apart with nms 10: only exact duplicates suppress each other."""
+    pred, cls = _lattice_points(seed, B, n, C)
+    wants = _decode_vs_oracle(gpu, pred, cls, conf, top_k, 10.0)
+    per_class = [sum(1 for w in wants[0] if w[0] == c) for c in range(C)]
+    if top_k == 64:
+        assert min(per_class) == 64
+    if n == 1:
+        assert sum(len(w) for w in wants) >= 1
+
+
+def test_ssd_decode_equal_scores_keep_index_order(gpu):
+    """Twenty anchors with one logit row (equal scores, bit for bit) far apart, among 237 that do not
+    pass: the kept ones are the lowest indices, in index order (the sort's index tie-break)."""
+    n, top_k = 257, 8
+    g = torch.Generator().manual_seed(41)
+    same = torch.randperm(n, generator=g)[:20]
+    pred = torch.zeros(1, n, 2)
+    pred[0, :, 0] = torch.arange(n) * 40.0
+    cls = torch.zeros(1, n, 5)
+    cls[0, :, 4] = 6.0
+    cls[0, same] = torch.tensor([3.0, 0.5, -1.0, 0.25, 0.0])
+    wants = _decode_vs_oracle(gpu, pred, cls, 0.5, top_k, 20.0)
+    assert [w[2][0] for w in wants[0] if w[0] == 0] == [40.0 * int(i) for i in sorted(same.tolist())[:top_k]]
+
+
+@pytest.mark.parametrize("nms,kept", [(5.0, 2), (4.999, 4)])
+def test_ssd_decode_nms_boundary(gpu, nms, kept):
+    """Two pairs at a 3-4-5 offset: a point at distance exactly 5 from a kept one is suppressed at
+    nms 5 (<=: the tensor form keeps d > threshold), and survives at 4.999."""
+    pred = torch.tensor([[[100.0, 100.0], [103.0, 104.0], [300.0, 100.0], [296.0, 97.0]]])
+    cls = torch.tensor([[[4.0, 0, 0, 0, 0], [3.0, 0, 0, 0, 0], [2.0, 0, 0, 0, 0], [3.5, 0, 0, 0, 0]]])
+    wants = _decode_vs_oracle(gpu, pred, cls, 0.5, 8, nms)
+    pts = [w[2] for w in wants[0] if w[0] == 0]
+    assert len(pts) == kept and ([103.0, 104.0] in pts) == (kept == 4) and ([300.0, 100.0] in pts) == (kept == 4)
+
+
+def test_ssd_decode_writes_every_slot(gpu):
+    """tpg_ssd_decode into buffers filled with 7: the kept anchors first, then -1 with score 0 in
+    every remaining slot of all top_k (tpgan.h: "anchor index or -1"), not only in the first."""
+    import ctypes
+    from tpgan_lib import check, load, stream_ptr
+    lib = load()
+    B, n, C, top_k = 2, 40, 5, 64
+    pred, cls = _lattice_points(51, B, n, C)
+    loc_d, cls_d = pred.to(gpu).contiguous(), cls.to(gpu).contiguous()
+    for conf in (0.4, 1.0):  # some survivors per class / none (softmax never exceeds 1)
+        keep = torch.full((B, C, top_k), 7, dtype=torch.int32, device=gpu)
+        score = torch.full((B, C, top_k), 7.0, dtype=torch.float32, device=gpu)
+        check(lib.tpg_ssd_decode(B, n, C, ctypes.c_void_p(loc_d.data_ptr()), ctypes.c_void_p(cls_d.data_ptr()), conf,
+                                 10.0, top_k, ctypes.c_void_p(keep.data_ptr()), ctypes.c_void_p(score.data_ptr()),
+                                 stream_ptr()))
+        torch.cuda.synchronize()
+        keep, score = keep.cpu(), score.cpu()
+        for b in range(B):
+            want = O.decode(O.as_lists(pred[b].double()), O.as_lists(cls[b].double()), confidence_threshold=conf,
+                            top_k=top_k, nms_distance_threshold=10.0)
+            for c in range(C):
+                k = sum(1 for w in want if w[0] == c)
+                assert 0 <= k < top_k
+                assert [pred[b, j].tolist() for j in keep[b, c, :k].tolist()] == [w[2] for w in want if w[0] == c]
+                assert keep[b, c, k:].tolist() == [-1] * (top_k - k) and score[b, c, k:].tolist() == [0.0] * (top_k - k)
+        if conf == 1.0:
+            import MobileNetV2 as M
+            assert M.MultiTaskDecoder(confidence_threshold=1.0, top_k=top_k, nms_distance_threshold=10.0)(
+                loc_d, cls_d) == [[] for _ in range(B)]
+
+
+@pytest.mark.parametrize("top_k", [100, 0])
+def test_ssd_decoder_top_k_outside_kernel_range(gpu, top_k):
+    """top_k outside the kernel's 1..64 takes the tensor form on the device: what the CPU gives."""
+    import MobileNetV2 as M
+    pred, cls = _lattice_points(61, 2, 300, 5)
+    dec = M.MultiTaskDecoder(confidence_threshold=0.3, top_k=top_k, nms_distance_threshold=10.0)
+    got, want = dec(pred.to(gpu), cls.to(gpu)), dec(pred, cls)
+    assert len(got) == len(want) == 2
+    for g_, w_ in zip(got, want):
+        assert len(g_) == len(w_) and (top_k > 0) == (len(w_) > 0)
+        for (c, s, p), (wc, ws, wp) in zip(g_, w_):
+            assert c == wc and float(s) == pytest.approx(float(ws), rel=1e-5) and p.tolist() == wp.tolist()
+    if top_k == 100:
+        assert max(sum(1 for r in w_ if r[0] == c) for w_ in want for c in range(5)) > 64

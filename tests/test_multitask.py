@@ -164,6 +164,106 @@ def test_find_best_coordinates():
         assert torch.allclose(out[name], loc[0, keep, 2 * j:2 * j + 2].mean(0))
 
 
+# ---- lattice cases: inputs on which fp32 and fp64 must agree on every label, ties included -------
+# Predictions are 16 * randint(-8, 49) (-128 .. 768 on a 640 x 480 image: anchors left of, right of,
+# above and below it, and exactly on 0 / 640 / 480), landmarks 16 * randint(2, 28) + 8.  A squared
+# distance is then an integer below 2^21, exact in fp32, and the correctly rounded fp32 square roots
+# of two distinct integers of that size are distinct (neighbouring roots differ by more than
+# 1 / (2 * 1100) = 4.5e-4, an fp32 ulp below 1024 is at most 6.1e-5) and ordered as the fp64 ones.  So the HIP
+# kernel, the fp32 tensor form and the fp64 tensor form see the same order and the same ties, and
+# tests/test_gpu_ssd.py may demand exact labels of the kernel with the fp64 tensor form as reference.
+IMAGE = (480, 640)  # (height, width)
+
+
+def lattice_case(seed, B, n, C=5, truth_out=False):
+    g = torch.Generator().manual_seed(seed)
+    pred = (16 * torch.randint(-8, 49, (B, n, 2), generator=g)).float()
+    true = (16 * torch.randint(2, 28, (B, 8), generator=g) + 8).float()
+    if truth_out:  # landmark 0 left of the image, landmark 3 below it (still on the landmark lattice)
+        true[:, 0] = -24.0
+        true[:, 7] = 504.0
+    cls = torch.randn(B, n, C, generator=g) * 2
+    return pred, cls, true
+
+
+# name -> seed, B, n, ratio, C, truth outside the image, what the case plants ("tie": an anchor
+# positive for and equidistant from two landmarks; "outside" / "edge": a positive with a coordinate
+# outside [0, size] / exactly on 0 or size whose clamped target differs), and the ratio_nb values
+# with the background path each gives in at least one image ("all": every background anchor,
+# "draw": the cap smallest keys, "cap0": int(#positives * ratio_nb) == 0, no background term).
+# The seeds are the first ones that satisfy this, found on the CPU with the tensor form.
+LATTICE_CASES = {
+    "257": dict(seed=0, B=2, n=257, ratio=0.1, C=5, truth_out=False, plants=("tie", "outside", "edge"),
+                nb=((5.0, "all"), (0.5, "draw"), (0.0, "cap0"))),
+    "4096": dict(seed=1, B=1, n=4096, ratio=0.05, C=5, truth_out=True, plants=("tie", "outside", "edge"),
+                 nb=((5.0, "all"), (0.5, "draw"))),
+    "4095": dict(seed=0, B=2, n=4095, ratio=0.02, C=7, truth_out=False, plants=("tie", "outside", "edge"),
+                 nb=((0.5, "draw"), (0.001, "cap0"))),
+    "40": dict(seed=4, B=3, n=40, ratio=0.25, C=5, truth_out=True, plants=("tie", "outside", "edge"),
+               nb=((5.0, "all"), (0.1, "draw"))),
+    "12": dict(seed=0, B=1, n=12, ratio=0.25, C=5, truth_out=False, plants=(), nb=((5.0, "all"), (0.0, "cap0"))),
+}
+
+
+def lattice_inputs(name):
+    c = LATTICE_CASES[name]
+    return lattice_case(c["seed"], c["B"], c["n"], c["C"], c["truth_out"])
+
+
+def lattice_stats(pred, true, ratio):
+    """fp64 tensor-form labels of a lattice case and the masks of what it plants."""
+    M = _mods()
+    B, n, _ = pred.shape
+    _, lab = M.MultiTaskLoss(distance_threshold_ratio=ratio).get_positive_samples_and_classification_tensor(
+        pred.double(), true.double())
+    lab = lab.long()
+    t = true.double().reshape(B, 4, 2)
+    d = torch.cdist(pred.double(), t)
+    thr = d.topk(int(ratio * n), dim=1, largest=False)[0].amax(dim=1, keepdim=True)
+    dm = torch.where(d <= thr, d, torch.full_like(d, float("inf")))
+    tie = (lab >= 0) & ((dm == dm.amin(dim=2, keepdim=True)).sum(dim=2) >= 2)
+    size = torch.tensor([IMAGE[1], IMAGE[0]], dtype=torch.float64)
+    p = pred.double()
+    posi = (lab >= 0).unsqueeze(2)
+    tsel = t[torch.arange(B).unsqueeze(1), lab.clamp(min=0)]  # (B, n, 2): the landmark of each positive
+    moves = torch.clamp(tsel / size, 0, 1) != torch.clamp(p / size, 0, 1)
+    return dict(labels=lab, tie=tie, outside=posi & ((p < 0) | (p > size)),
+                edge=posi & ((p == 0) | (p == size)) & moves)
+
+
+def tensor_form_loss(pred, cls, true, ratio, ratio_nb, dtype, key_seed=7):
+    """MultiTaskLoss's tensor form on the CPU in `dtype`, its background keys torch.rand after
+    manual_seed(key_seed) (fp32 in either dtype: the same draw)."""
+    M = _mods()
+    m = M.MultiTaskLoss(distance_threshold_ratio=ratio, ratio_non_background=ratio_nb)
+    torch.manual_seed(key_seed)
+    return m(pred.to(dtype), cls.to(dtype), true.to(dtype), IMAGE)
+
+
+@pytest.mark.parametrize("name", list(LATTICE_CASES))
+def test_lattice_cases_hold_their_condition(name):
+    """What tests/test_gpu_ssd.py relies on, for every lattice case it uses: (a) the tensor form gives
+    the same labels in fp32 and fp64, (b) the case contains what it is meant to plant and its ratio_nb
+    values take the background paths they name, (c) the fp32 and fp64 losses agree to 1e-6."""
+    M = _mods()
+    c = LATTICE_CASES[name]
+    pred, cls, true = lattice_inputs(name)
+    st = lattice_stats(pred, true, c["ratio"])
+    _, lab32 = M.MultiTaskLoss(distance_threshold_ratio=c["ratio"]).get_positive_samples_and_classification_tensor(
+        pred, true)
+    assert torch.equal(lab32.long(), st["labels"])                                   # (a)
+    for what in c["plants"]:                                                         # (b)
+        assert int(st[what].sum()) >= 1, what
+    nbg = (st["labels"] == -1).sum(dim=1)
+    for ratio_nb, path in c["nb"]:
+        cap = ((c["n"] - nbg).double() * ratio_nb).floor().long()
+        got = ["cap0" if int(k) == 0 else "all" if int(b) <= int(k) else "draw" for b, k in zip(nbg, cap)]
+        assert path in got, (ratio_nb, path, got)
+        l32 = float(tensor_form_loss(pred, cls, true, c["ratio"], ratio_nb, torch.float32))
+        l64 = float(tensor_form_loss(pred, cls, true, c["ratio"], ratio_nb, torch.float64))
+        assert l32 == pytest.approx(l64, rel=1e-6), (ratio_nb, l32, l64)             # (c)
+
+
 @pytest.mark.gpu
 def test_known_answer_on_gpu(gpu):
     loss, dec = _known_answer(gpu)

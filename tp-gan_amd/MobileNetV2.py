@@ -353,8 +353,9 @@ class MultiTaskDecoder(nn.Module):
 
     def forward(self, locations, classifications):
         if (locations.is_cuda and locations.shape[1] <= 4096 and classifications.shape[2] >= 5 and
-                locations.dtype != torch.float64):
-            # (tpg_ssd_decode: one block per image and class; the kept points in score order)
+                locations.dtype != torch.float64 and 1 <= self.top_k <= 64):
+            # (tpg_ssd_decode: one block per image and class; the kept points in score order.  It
+            # keeps at most 64 per class: any other top_k takes the tensor form below)
             keep, score = tpgan_ops.ssd_decode(locations, classifications, self.confidence_threshold,
                                                self.nms_distance_threshold, self.top_k)
             keep, score = keep.cpu(), score.cpu()

@@ -274,8 +274,12 @@ __global__ __launch_bounds__(SSD_T) void ssd_decode_kernel(const SsdDecArgs a) {
       for (int i = 0; i < n2 && p < 0; ++i)
         if (alive[i]) p = i;  // (the highest remaining score: sorted order)
       pick = p;
-      K[r] = p < 0 ? -1 : idx[p];
-      S[r] = p < 0 ? 0.f : -key[p];
+      if (p < 0) {  // exhausted: this and every later slot is empty (the "or -1" of tpgan.h)
+        for (int q = r; q < a.top_k; ++q) { K[q] = -1; S[q] = 0.f; }
+      } else {
+        K[r] = idx[p];
+        S[r] = -key[p];
+      }
     }
     __syncthreads();
     const int p = pick;

@@ -1696,6 +1696,8 @@ class _Maxout2(torch.autograd.Function):
         (amax,) = ctx.saved_tensors
         b, k = ctx.shape
         dx = torch.empty((b, k), dtype=ctx.dtype, device=gy.device)
+        if k % 2:  # the forward drops the last feature of an odd row: its gradient is 0 (MaxPool1d(2, 2))
+            dx[:, k - 1].zero_()
         check(lib.tpg_maxout2_bwd(b, k // 2, tt(gy), amax.data_ptr(), tt(dx), stream_ptr()))
         return dx
 
