@@ -178,7 +178,7 @@ int32_t tpg_conv2d_bwd_filter(const tpg_conv_desc* d, tpg_tensor x, tpg_tensor g
  * nothing dereferenced, nothing launched or flushed.  Returns what tpg_conv2d_bwd_filter would
  * return before its first launch (0, or e.g. -30 for a desc.algo that does not cover the shape;
  * *out is then untouched).  Reads the same process state as the launch: desc.flags CONCURRENT,
- * tpg_set_deterministic, TPG_RH_SKIP. */
+ * tpg_set_deterministic. */
 enum { TPG_WGRAD_GENERIC = 0, TPG_WGRAD_FLAT = 1, TPG_WGRAD_ROW_HALO = 2, TPG_WGRAD_IMAGE_HALO = 3 };
 enum {
   TPG_WGRAD_SUMS_BIAS = 1, /* the launch adds the bias gradient when given one (tpg_conv2d_bwd) */

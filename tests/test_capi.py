@@ -35,9 +35,19 @@ def test_header_matches_binding():
 
 
 def test_exports(lib):
+    """The library's defined `T tpg_*` dynamic symbols are exactly the header's functions: nothing
+    missing, and no internal launcher exported with C linkage beside them."""
+    import shutil
+    import subprocess
     for name in header_functions():
         assert hasattr(lib, name), name
     assert lib.tpg_version().decode().startswith("tpgan_hip")
+    nm = shutil.which("nm") or shutil.which("llvm-nm", path="/opt/rocm/lib/llvm/bin")  # (the Makefile's LLVM_BIN)
+    if nm is None:
+        pytest.skip("nm not installed")
+    out = subprocess.run([nm, "-D", "--defined-only", L.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = sorted(m.group(1) for m in re.finditer(r"^\S+ T (tpg_\w+)$", out, flags=re.M))
+    assert exported == header_functions()
 
 
 def _desc(n, cin, h, w, cout, k, s, p, transposed=False, op=0, reflect=False, dtype=L.TPG_BF16):
@@ -123,6 +133,14 @@ def test_null_tensor_rejected_without_device_work(lib):
     z = L.TpgTensor()
     rc = lib.tpg_conv2d_fwd(ctypes.byref(d), z, z, None, z, z, None, 0, None)
     assert rc < 0 and b"NULL" in lib.tpg_last_error()
+    # one entry point per kernel file (features, image, identity): the same status as ever, and
+    # the message names the call -- they share the conv entry points' error plumbing
+    for call, name in ((lambda: lib.tpg_avgpool_fwd(1, 16, 8, 8, z, z, None), b"avgpool"),
+                       (lambda: lib.tpg_denorm_u8(1, 3, 8, 8, z, None, None), b"denorm_u8"),
+                       (lambda: lib.tpg_l2_normalize(1, 4, z, None, 4, None, None, None), b"l2_normalize")):
+        lib.tpg_conv2d_fwd(ctypes.byref(d), z, z, None, z, z, None, 0, None)  # (an unrelated earlier failure)
+        assert call() == -10
+        assert name in lib.tpg_last_error() and b"NULL" in lib.tpg_last_error()
 
 
 def test_wgrad_plans_match_recorded(lib):

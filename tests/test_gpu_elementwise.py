@@ -393,7 +393,7 @@ def test_adam_sliced_equals_whole(gpu):
 
 def test_adam_rejects_mixed_offsets(gpu):
     """A grad pointer at another offset inside 16 bytes than param's is refused by the host-side
-    check before any launch (tpg_adam_impl's -1, which the public entry point reports as -15 with
+    check before any launch (tpg::launch_adam's -1, which the public entry point reports as -15 with
     a message): state, parameters and moments stay as they were."""
     from tpgan_lib import load, stream_ptr
     lib = load()

@@ -394,6 +394,51 @@ def test_local_pathways_grouped_equal_per_patch(gpu, dtype, flat):
         assert bool(torch.isfinite(u).all()) and float(u.abs().max()) > 0, name
 
 
+def test_group_flushes_before_ungrouped_entry_point(gpu):
+    """include/tpgan.h: inside a launch group "a call that needs another kernel flushes the record
+    first, so the semantics are always those of the calls run in order" -- also for the entry
+    points of the kernel files.  The C ABI directly: a recorded halo conv (the plan says so; 16
+    channels keep it off the pointwise kernel) into a zero-filled y, then tpg_avgpool_fwd(y -> m)
+    before the group ends.  m is bit-equal to the same two calls outside a group, and not the
+    average of the zero fill."""
+    import ctypes
+    import tpgan_lib as L
+    lib = L.load()
+    N, C, H, W, k = 1, 16, 8, 8, 3
+    gen = torch.Generator().manual_seed(13)
+    x = (torch.rand(N, H, W, C, generator=gen) + 0.5).to(gpu).bfloat16().permute(0, 3, 1, 2)
+    w = (torch.rand(C, C, k, k, generator=gen) + 0.5).to(gpu).contiguous(memory_format=torch.channels_last)
+    d = L.ConvDesc(n=N, in_c=C, in_h=H, in_w=W, out_c=C, out_h=H, out_w=W, kh=k, kw=k, stride_h=1, stride_w=1,
+                   pad_t=1, pad_b=1, pad_l=1, pad_r=1, dtype=L.TPG_BF16, res_scale=1.0)
+    ws = lib.tpg_conv2d_workspace(ctypes.byref(d), L.OP_FWD)
+    buf = torch.zeros(ws, device=gpu, dtype=torch.uint8)
+    none, plan = L.TpgTensor(), L.DataPlan()
+
+    def run(group):
+        y = torch.zeros(N, H, W, C, device=gpu, dtype=torch.bfloat16).permute(0, 3, 1, 2)
+        m = torch.full((N, C), -1.0, device=gpu, dtype=torch.bfloat16)
+        L.check(lib.tpg_conv2d_data_plan(ctypes.byref(d), L.OP_FWD, L.tt(x), L.tt(y), none, none, none, ws,
+                                         ctypes.byref(plan)))
+        assert plan.nprobs == 1 and L.DATA_KERNELS[plan.prob[0].kernel] == "halo"
+        torch.cuda.synchronize()
+        if group:
+            lib.tpg_group_begin()
+            lib.tpg_group_member()
+        try:
+            L.check(lib.tpg_conv2d_fwd(ctypes.byref(d), L.tt(x), L.tt(w), None, none, L.tt(y), buf.data_ptr(), ws,
+                                       L.stream_ptr()))
+            L.check(lib.tpg_avgpool_fwd(N, C, H, W, L.tt(y), L.tt(m), L.stream_ptr()))
+        finally:
+            if group:
+                L.check(lib.tpg_group_end())
+        torch.cuda.synchronize()
+        return m
+
+    plain, grouped = run(False), run(True)
+    assert float(plain.float().min()) > 0  # (positive inputs and weights: every mean is positive)
+    assert torch.equal(grouped, plain) and bool((grouped != 0).any())
+
+
 def test_local_pathways_grouped_nondeterministic(gpu):
     """Default (split) mode: grouped and per-patch runs agree to summation-order rounding."""
     import D_and_G_model as DG

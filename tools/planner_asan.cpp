@@ -1,4 +1,5 @@
-// Host-side AddressSanitizer sweep of the convolution planner (tpg_capi.hip).
+// Host-side AddressSanitizer sweep of the convolution planner (tpg_plan_data.hip,
+// tpg_plan_wgrad.hip) through the entry points of tpg_capi.hip.
 //
 // The planner (check_desc -> plan_data / plan_probs / maybe_halo / plan_bwd_filter ->
 // workspace and pre-pack sizing) is pure host code: it runs before any launch and sizes the
@@ -23,7 +24,7 @@
 // of (P, G, k, gchunk) up to 2^24 rows, whose size must be positive, hold at least one k-entry list
 // per probe and chunk and not shrink when P or the number of chunks grows, and every argument the
 // three launch entry points reject (which must stop them before any device work).
-// Built with `make -C tp-gan_amd asan` (planner object compiled with -fsanitize=address on
+// Built with `make -C tp-gan_amd asan` (the host-logic units compiled with -fsanitize=address on
 // the host side only; the kernels are the product's) and run by tests/test_capi.py.
 // Exit status: 0 clean, 1 a consistency check failed; ASan aborts on a memory error.
 #include <cstdint>

@@ -132,9 +132,10 @@ using namespace tpg;
 extern "C" int32_t tpg_landmark_boxes(int32_t n, int32_t npts, const float* lm, const float* scale,
                                       const int32_t* pts_idx, const int32_t* patch_wh, float* lm5, int32_t* boxes,
                                       int32_t* status, tpg_stream_t stream) {
+  if (int32_t grc = group_sync()) return grc;
   if (n == 0) return 0;
-  if (n < 0 || npts <= 0) return record_error(-2, "landmark_boxes: bad sizes");
-  if (!lm || !pts_idx || !patch_wh || !lm5 || !boxes || !status) return record_error(-10, "landmark_boxes: NULL pointer");
+  if (n < 0 || npts <= 0) return fail(-2, "landmark_boxes: bad sizes");
+  if (!lm || !pts_idx || !patch_wh || !lm5 || !boxes || !status) return fail(-10, "landmark_boxes: NULL pointer");
   LmArgs a;
   for (int j = 0; j < 5; ++j) {
     a.lo[j] = pts_idx[2 * j];
@@ -143,22 +144,22 @@ extern "C" int32_t tpg_landmark_boxes(int32_t n, int32_t npts, const float* lm, 
   for (int i = 0; i < 4; ++i) {
     a.pw[i] = patch_wh[2 * i];
     a.ph[i] = patch_wh[2 * i + 1];
-    if (a.pw[i] <= 0 || a.ph[i] <= 0) return record_error(-2, "landmark_boxes: bad patch size");
+    if (a.pw[i] <= 0 || a.ph[i] <= 0) return fail(-2, "landmark_boxes: bad patch size");
   }
   hipLaunchKernelGGL(landmark_boxes_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, n, npts, lm, scale,
                      a, lm5, boxes, status);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : record_error((int)e, hipGetErrorString(e));
+  return launched("landmark_boxes");
 }
 
 extern "C" int32_t tpg_crop_normalize(int32_t n, int32_t c, int32_t in_h, int32_t in_w, const uint8_t* img,
                                       const int64_t* img_stride, int32_t njobs, const tpg_tensor* outs,
                                       const int32_t* out_hw, const int32_t* slots, const int32_t* boxes,
                                       int32_t box_stride, tpg_stream_t stream) {
+  if (int32_t grc = group_sync()) return grc;
   if (n == 0 || njobs == 0) return 0;
-  if (n < 0 || c <= 0 || in_h <= 0 || in_w <= 0 || njobs < 0) return record_error(-2, "crop_normalize: bad sizes");
-  if (njobs > MAX_JOBS) return record_error(-2, "crop_normalize: at most 8 jobs per launch");
-  if (!img || !img_stride || !outs || !out_hw || !slots) return record_error(-10, "crop_normalize: NULL pointer");
+  if (n < 0 || c <= 0 || in_h <= 0 || in_w <= 0 || njobs < 0) return fail(-2, "crop_normalize: bad sizes");
+  if (njobs > MAX_JOBS) return fail(-2, "crop_normalize: at most 8 jobs per launch");
+  if (!img || !img_stride || !outs || !out_hw || !slots) return fail(-10, "crop_normalize: NULL pointer");
   CropArgs a;
   a.img = img;
   for (int i = 0; i < 4; ++i) a.is[i] = img_stride[i];
@@ -175,13 +176,12 @@ extern "C" int32_t tpg_crop_normalize(int32_t n, int32_t c, int32_t in_h, int32_
     j.h = out_hw[2 * k];
     j.w = out_hw[2 * k + 1];
     j.slot = slots[k];
-    if (!j.out.data) return record_error(-10, "crop_normalize: output NULL");
-    if (j.out.dtype != TPG_F32 && j.out.dtype != TPG_BF16) return record_error(-3, "crop_normalize: bad dtype");
-    if (j.h <= 0 || j.w <= 0) return record_error(-2, "crop_normalize: bad output size");
-    if (j.slot >= 0 && (!boxes || 4 * j.slot + 2 > box_stride)) return record_error(-2, "crop_normalize: bad box slot");
+    if (!j.out.data) return fail(-10, "crop_normalize: output NULL");
+    if (j.out.dtype != TPG_F32 && j.out.dtype != TPG_BF16) return fail(-3, "crop_normalize: bad dtype");
+    if (j.h <= 0 || j.w <= 0) return fail(-2, "crop_normalize: bad output size");
+    if (j.slot >= 0 && (!boxes || 4 * j.slot + 2 > box_stride)) return fail(-2, "crop_normalize: bad box slot");
     if (j.h * j.w > maxpix) maxpix = j.h * j.w;
   }
   hipLaunchKernelGGL(crop_norm_kernel, dim3((maxpix + 255) / 256, njobs, n), dim3(256), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : record_error((int)e, hipGetErrorString(e));
+  return launched("crop_normalize");
 }

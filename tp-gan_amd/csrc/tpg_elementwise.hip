@@ -460,9 +460,9 @@ __global__ __launch_bounds__(256) void unfold_taps_kernel(int N, int C, int H, i
   }
 }
 
-extern "C" int32_t tpg_fold_taps_impl(int32_t n, int32_t c, int32_t h, int32_t w, int32_t fh, int32_t fw, int32_t sh,
-                                      int32_t sw, int32_t pt, int32_t pl, int32_t oh, int32_t ow, tpg_tensor x,
-                                      tpg_tensor y, int32_t backward, hipStream_t s) {
+int launch_fold_taps(int32_t n, int32_t c, int32_t h, int32_t w, int32_t fh, int32_t fw, int32_t sh,
+                     int32_t sw, int32_t pt, int32_t pl, int32_t oh, int32_t ow, tpg_tensor x,
+                     tpg_tensor y, int32_t backward, hipStream_t s) {
   if (backward)
     hipLaunchKernelGGL(unfold_taps_kernel, dim3(grid_for((int64_t)n * h * w * c)), dim3(256), 0, s, n, c, h, w, fh, fw,
                        sh, sw, pt, pl, oh, ow, y, x);
@@ -791,10 +791,8 @@ int launch_act_vec_group(const ActVecArgs* a, int n, int dtype, hipStream_t s) {
   launch_act_vec_t<TPG_GROUP_MAX>(g, blocks, dtype, s);
   return (int)hipGetLastError();
 }
-}  // namespace tpg
-
-extern "C" int32_t tpg_act_bwd_impl(int32_t n, int32_t c, int32_t h, int32_t w, int32_t act, float slope,
-                                     tpg_tensor gy, tpg_tensor y, tpg_tensor g, float* dbias, hipStream_t s) {
+int launch_act_bwd(int32_t n, int32_t c, int32_t h, int32_t w, int32_t act, float slope,
+                   tpg_tensor gy, tpg_tensor y, tpg_tensor g, float* dbias, hipStream_t s) {
   const int dt = g.dtype;
   ActVecArgs a;
   if (act_vec_args(n, c, h, w, act, slope, gy, y, g, dbias, &a) == 0) return launch_act_vec(a, dt, s);
@@ -816,8 +814,8 @@ extern "C" int32_t tpg_act_bwd_impl(int32_t n, int32_t c, int32_t h, int32_t w, 
   return (int)hipGetLastError();
 }
 
-extern "C" int32_t tpg_colsum_impl(int32_t n, int32_t c, int32_t h, int32_t w, tpg_tensor g, float* dbias,
-                                    hipStream_t s) {
+int launch_colsum(int32_t n, int32_t c, int32_t h, int32_t w, tpg_tensor g, float* dbias,
+                  hipStream_t s) {
   const int64_t npix = (int64_t)n * h * w;
   // pixel-dense 16-bit rows: the activation-backward vector kernel with no output (16-byte loads,
   // several pixels in flight per lane; the generic loop below divided 64-bit pixel indices per
@@ -838,8 +836,8 @@ extern "C" int32_t tpg_colsum_impl(int32_t n, int32_t c, int32_t h, int32_t w, t
   return (int)hipGetLastError();
 }
 
-extern "C" int32_t tpg_copy4d_impl(int32_t n, int32_t c, int32_t h, int32_t w, tpg_tensor in, tpg_tensor out,
-                                    hipStream_t s) {
+int launch_copy4d(int32_t n, int32_t c, int32_t h, int32_t w, tpg_tensor in, tpg_tensor out,
+                  hipStream_t s) {
   const int G = (c + 7) / 8;
   if ((int64_t)n * h * w * G < (1ll << 31) - 256) {
     // 16-byte groups: 16-bit dtype, channel stride 1, every group start 16-byte aligned
@@ -856,9 +854,9 @@ extern "C" int32_t tpg_copy4d_impl(int32_t n, int32_t c, int32_t h, int32_t w, t
   return (int)hipGetLastError();
 }
 
-extern "C" int32_t tpg_fuse_fwd_impl(int32_t n, int32_t c, int32_t oh, int32_t ow, const tpg_tensor* parts,
-                                      const int32_t* ph, const int32_t* pw, const int32_t* top, const int32_t* left,
-                                      tpg_tensor y, uint8_t* amax, hipStream_t s) {
+int launch_fuse_fwd(int32_t n, int32_t c, int32_t oh, int32_t ow, const tpg_tensor* parts,
+                    const int32_t* ph, const int32_t* pw, const int32_t* top, const int32_t* left,
+                    tpg_tensor y, uint8_t* amax, hipStream_t s) {
   FuseGeom g;
   for (int k = 0; k < 4; ++k) {
     g.part[k] = parts[k]; g.ph[k] = ph[k]; g.pw[k] = pw[k]; g.top[k] = top[k]; g.left[k] = left[k];
@@ -868,9 +866,9 @@ extern "C" int32_t tpg_fuse_fwd_impl(int32_t n, int32_t c, int32_t oh, int32_t o
   return (int)hipGetLastError();
 }
 
-extern "C" int32_t tpg_fuse_bwd_impl(int32_t n, int32_t c, int32_t oh, int32_t ow, tpg_tensor gy, const uint8_t* amax,
-                                      const tpg_tensor* dparts, const int32_t* ph, const int32_t* pw,
-                                      const int32_t* top, const int32_t* left, hipStream_t s) {
+int launch_fuse_bwd(int32_t n, int32_t c, int32_t oh, int32_t ow, tpg_tensor gy, const uint8_t* amax,
+                    const tpg_tensor* dparts, const int32_t* ph, const int32_t* pw,
+                    const int32_t* top, const int32_t* left, hipStream_t s) {
   for (int k = 0; k < 4; ++k) {
     if (!dparts[k].data) continue;
     hipLaunchKernelGGL(fuse_bwd_kernel, dim3(grid_for((int64_t)n * ph[k] * pw[k] * c)), dim3(256), 0, s, n, c, oh,
@@ -879,22 +877,22 @@ extern "C" int32_t tpg_fuse_bwd_impl(int32_t n, int32_t c, int32_t oh, int32_t o
   return (int)hipGetLastError();
 }
 
-extern "C" int32_t tpg_maxout_fwd_impl(int32_t b, int32_t m, tpg_tensor x, tpg_tensor y, uint8_t* amax, hipStream_t s) {
+int launch_maxout_fwd(int32_t b, int32_t m, tpg_tensor x, tpg_tensor y, uint8_t* amax, hipStream_t s) {
   hipLaunchKernelGGL(maxout_fwd_kernel, dim3(grid_for((int64_t)b * m)), dim3(256), 0, s, b, m, x, y, amax);
   return (int)hipGetLastError();
 }
 
-extern "C" int32_t tpg_maxout_bwd_impl(int32_t b, int32_t m, tpg_tensor gy, const uint8_t* amax, tpg_tensor dx,
-                                        hipStream_t s) {
+int launch_maxout_bwd(int32_t b, int32_t m, tpg_tensor gy, const uint8_t* amax, tpg_tensor dx,
+                      hipStream_t s) {
   hipLaunchKernelGGL(maxout_bwd_kernel, dim3(grid_for((int64_t)b * 2 * m)), dim3(256), 0, s, b, m, gy, amax, dx);
   return (int)hipGetLastError();
 }
 
 // state: device float[4] {step, 1-b1^t, sqrt(1-b2^t), -}; host_step > 0 sets the step
 // explicitly, 0 advances the device counter (graph replay).
-extern "C" int32_t tpg_adam_impl(int64_t numel, float* param, const float* grad, float* m, float* v, float lr,
-                                  float b1, float b2, float eps, float wd, int32_t host_step, float gscale,
-                                  float* state, hipStream_t s) {
+int launch_adam(int64_t numel, float* param, const float* grad, float* m, float* v, float lr,
+                float b1, float b2, float eps, float wd, int32_t host_step, float gscale,
+                float* state, hipStream_t s) {
   // argument checks before any launch: an error must not advance the device step counter
   // the four buffers must share their offset inside a 16-byte chunk (elements of one flat layout)
   const uintptr_t mis = (uintptr_t)param % 16;
@@ -913,7 +911,7 @@ extern "C" int32_t tpg_adam_impl(int64_t numel, float* param, const float* grad,
   return (int)hipGetLastError();
 }
 
-extern "C" int32_t tpg_grad_check_impl(int64_t numel, const float* grad, float* state, hipStream_t s) {
+int launch_grad_check(int64_t numel, const float* grad, float* state, hipStream_t s) {
   if (((uintptr_t)grad) % 16) return -1;
   hipError_t e = hipMemsetAsync(state + 3, 0, sizeof(float), s);
   if (e) return (int)e;
@@ -923,3 +921,4 @@ extern "C" int32_t tpg_grad_check_impl(int64_t numel, const float* grad, float* 
   hipLaunchKernelGGL(grad_finite_kernel, dim3(blocks), dim3(256), 0, s, numel, grad, state);
   return (int)hipGetLastError();
 }
+}  // namespace tpg

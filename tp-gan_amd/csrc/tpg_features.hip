@@ -508,8 +508,6 @@ using namespace tpg;
 
 namespace {
 
-int ffail(int code, const char* msg) { return tpg::record_error(code, msg); }
-
 inline int grid_cap(int64_t total, int cap = 8192) {
   int64_t b = (total + 255) / 256;
   return (int)(b < 1 ? 1 : (b > cap ? cap : b));
@@ -524,14 +522,14 @@ bool chunk_ok(const tpg_tensor& t, int C) {
 }
 
 int dw_check(const tpg_conv_desc* d) {
-  if (!d) return ffail(-1, "null descriptor");
+  if (!d) return fail(-1, "null descriptor");
   if (d->in_c != d->out_c || d->transposed || d->pad_mode != TPG_PAD_ZERO)
-    return ffail(-2, "depthwise: in_c must equal out_c, zero padding, no transposition");
-  if (d->kh * d->kw > 9 || d->kh < 1 || d->kw < 1) return ffail(-4, "depthwise: kernels up to 3x3");
-  if (d->dtype != TPG_F32 && d->dtype != TPG_BF16 && d->dtype != TPG_F16) return ffail(-3, "bad dtype");
+    return fail(-2, "depthwise: in_c must equal out_c, zero padding, no transposition");
+  if (d->kh * d->kw > 9 || d->kh < 1 || d->kw < 1) return fail(-4, "depthwise: kernels up to 3x3");
+  if (d->dtype != TPG_F32 && d->dtype != TPG_BF16 && d->dtype != TPG_F16) return fail(-3, "bad dtype");
   const int oh = (d->in_h + d->pad_t + d->pad_b - d->kh) / d->stride_h + 1;
   const int ow = (d->in_w + d->pad_l + d->pad_r - d->kw) / d->stride_w + 1;
-  if (oh != d->out_h || ow != d->out_w) return ffail(-6, "depthwise: output size inconsistent with geometry");
+  if (oh != d->out_h || ow != d->out_w) return fail(-6, "depthwise: output size inconsistent with geometry");
   return 0;
 }
 
@@ -563,11 +561,12 @@ dim3 dw_grid(DwArgs& a, int64_t npix, int per_lane, int cap) {
 
 extern "C" int32_t tpg_dwconv2d_fwd(const tpg_conv_desc* d, tpg_tensor x, tpg_tensor w, const float* bias,
                                     tpg_tensor residual, tpg_tensor y, tpg_stream_t stream) {
+  if (int32_t grc = group_sync()) return grc;
   if (int rc = dw_check(d)) return rc;
-  if (!x.data || !y.data || !w.data || w.dtype != TPG_F32) return ffail(-10, "depthwise fwd: NULL / bad tensor");
+  if (!x.data || !y.data || !w.data || w.dtype != TPG_F32) return fail(-10, "depthwise fwd: NULL / bad tensor");
   if (x.dtype != d->dtype || y.dtype != d->dtype || !chunk_ok(x, d->in_c) || !chunk_ok(y, d->out_c) ||
       (residual.data && (residual.dtype != d->dtype || !chunk_ok(residual, d->out_c))))
-    return ffail(-12, "depthwise: tensors must be 16-byte aligned channels-last rows of the compute dtype");
+    return fail(-12, "depthwise: tensors must be 16-byte aligned channels-last rows of the compute dtype");
   DwArgs a = dw_args(d, x, y, w);
   a.bias = bias;
   a.r_sn = residual.stride[0]; a.r_sh = residual.stride[2]; a.r_sw = residual.stride[3];
@@ -582,15 +581,16 @@ extern "C" int32_t tpg_dwconv2d_fwd(const tpg_conv_desc* d, tpg_tensor x, tpg_te
   else
     hipLaunchKernelGGL(dw_fwd_kernel<float>, grid, dim3(256), 0, s, a, (const float*)x.data, (float*)y.data,
                        (const float*)residual.data);
-  return (int)hipGetLastError();
+  return launched("dwconv2d_fwd");
 }
 
 extern "C" int32_t tpg_dwconv2d_bwd_data(const tpg_conv_desc* d, tpg_tensor g, tpg_tensor w, tpg_tensor dx,
                                          tpg_stream_t stream) {
+  if (int32_t grc = group_sync()) return grc;
   if (int rc = dw_check(d)) return rc;
-  if (!g.data || !dx.data || !w.data || w.dtype != TPG_F32) return ffail(-10, "depthwise dgrad: NULL / bad tensor");
+  if (!g.data || !dx.data || !w.data || w.dtype != TPG_F32) return fail(-10, "depthwise dgrad: NULL / bad tensor");
   if (g.dtype != d->dtype || dx.dtype != d->dtype || !chunk_ok(g, d->out_c) || !chunk_ok(dx, d->in_c))
-    return ffail(-12, "depthwise: tensors must be 16-byte aligned channels-last rows of the compute dtype");
+    return fail(-12, "depthwise: tensors must be 16-byte aligned channels-last rows of the compute dtype");
   DwArgs a = dw_args(d, dx, g, w);
   const dim3 grid = dw_grid(a, (int64_t)a.N * a.H * a.W, 4, 4096);
   hipStream_t s = (hipStream_t)stream;
@@ -600,15 +600,16 @@ extern "C" int32_t tpg_dwconv2d_bwd_data(const tpg_conv_desc* d, tpg_tensor g, t
     hipLaunchKernelGGL(dw_dgrad_kernel<__bf16>, grid, dim3(256), 0, s, a, (const __bf16*)g.data, (__bf16*)dx.data);
   else
     hipLaunchKernelGGL(dw_dgrad_kernel<float>, grid, dim3(256), 0, s, a, (const float*)g.data, (float*)dx.data);
-  return (int)hipGetLastError();
+  return launched("dwconv2d_bwd_data");
 }
 
 extern "C" int32_t tpg_dwconv2d_bwd_filter(const tpg_conv_desc* d, tpg_tensor x, tpg_tensor g, tpg_tensor dw,
                                            tpg_stream_t stream) {
+  if (int32_t grc = group_sync()) return grc;
   if (int rc = dw_check(d)) return rc;
-  if (!g.data || !x.data || !dw.data || dw.dtype != TPG_F32) return ffail(-10, "depthwise wgrad: NULL / bad tensor");
+  if (!g.data || !x.data || !dw.data || dw.dtype != TPG_F32) return fail(-10, "depthwise wgrad: NULL / bad tensor");
   if (g.dtype != d->dtype || x.dtype != d->dtype || !chunk_ok(g, d->out_c) || !chunk_ok(x, d->in_c))
-    return ffail(-12, "depthwise: tensors must be 16-byte aligned channels-last rows of the compute dtype");
+    return fail(-12, "depthwise: tensors must be 16-byte aligned channels-last rows of the compute dtype");
   DwArgs a = dw_args(d, x, g, dw);
   a.w = nullptr;
   const dim3 grid = dw_grid(a, (int64_t)a.N * a.OH * a.OW, 16, 256);
@@ -622,16 +623,17 @@ extern "C" int32_t tpg_dwconv2d_bwd_filter(const tpg_conv_desc* d, tpg_tensor x,
   else
     hipLaunchKernelGGL(dw_wgrad_kernel<float>, grid, dim3(256), 0, s, a, (const float*)x.data, (const float*)g.data,
                        (float*)dw.data);
-  return (int)hipGetLastError();
+  return launched("dwconv2d_bwd_filter");
 }
 
 extern "C" int32_t tpg_maxpool2d_fwd(int32_t n, int32_t c, int32_t h, int32_t w, int32_t k, int32_t s, int32_t p,
                                      int32_t oh, int32_t ow, tpg_tensor x, tpg_tensor y, uint8_t* argmax,
                                      tpg_stream_t stream) {
-  if (!x.data || !y.data || !argmax) return ffail(-10, "maxpool: NULL tensor");
-  if (k < 1 || k * k > 256 || s < 1 || p < 0 || 2 * p > k) return ffail(-2, "maxpool: bad geometry");
-  if (oh != (h + 2 * p - k) / s + 1 || ow != (w + 2 * p - k) / s + 1) return ffail(-6, "maxpool: bad output size");
-  if (x.dtype != y.dtype || x.stride[1] != 1 || y.stride[1] != 1) return ffail(-12, "maxpool: channels-last, one dtype");
+  if (int32_t grc = group_sync()) return grc;
+  if (!x.data || !y.data || !argmax) return fail(-10, "maxpool: NULL tensor");
+  if (k < 1 || k * k > 256 || s < 1 || p < 0 || 2 * p > k) return fail(-2, "maxpool: bad geometry");
+  if (oh != (h + 2 * p - k) / s + 1 || ow != (w + 2 * p - k) / s + 1) return fail(-6, "maxpool: bad output size");
+  if (x.dtype != y.dtype || x.stride[1] != 1 || y.stride[1] != 1) return fail(-12, "maxpool: channels-last, one dtype");
   hipStream_t st = (hipStream_t)stream;
   const int grid = grid_cap((int64_t)n * oh * ow * c);
   if (x.dtype == TPG_F16)
@@ -646,15 +648,16 @@ extern "C" int32_t tpg_maxpool2d_fwd(int32_t n, int32_t c, int32_t h, int32_t w,
     hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, n, c, h, w, oh, ow, k, s, p,
                        (const float*)x.data, x.stride[0], x.stride[2], x.stride[3], (float*)y.data, y.stride[0],
                        y.stride[2], y.stride[3], argmax);
-  return (int)hipGetLastError();
+  return launched("maxpool2d_fwd");
 }
 
 extern "C" int32_t tpg_maxpool2d_bwd(int32_t n, int32_t c, int32_t h, int32_t w, int32_t k, int32_t s, int32_t p,
                                      int32_t oh, int32_t ow, tpg_tensor gy, const uint8_t* argmax, tpg_tensor dx,
                                      tpg_stream_t stream) {
-  if (!gy.data || !dx.data || !argmax) return ffail(-10, "maxpool bwd: NULL tensor");
-  if (k < 1 || k * k > 256 || s < 1 || p < 0) return ffail(-2, "maxpool: bad geometry");
-  if (gy.dtype != dx.dtype || gy.stride[1] != 1 || dx.stride[1] != 1) return ffail(-12, "maxpool: channels-last");
+  if (int32_t grc = group_sync()) return grc;
+  if (!gy.data || !dx.data || !argmax) return fail(-10, "maxpool bwd: NULL tensor");
+  if (k < 1 || k * k > 256 || s < 1 || p < 0) return fail(-2, "maxpool: bad geometry");
+  if (gy.dtype != dx.dtype || gy.stride[1] != 1 || dx.stride[1] != 1) return fail(-12, "maxpool: channels-last");
   hipStream_t st = (hipStream_t)stream;
   const int grid = grid_cap((int64_t)n * h * w * c);
   if (gy.dtype == TPG_F16)
@@ -669,13 +672,14 @@ extern "C" int32_t tpg_maxpool2d_bwd(int32_t n, int32_t c, int32_t h, int32_t w,
     hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, n, c, h, w, oh, ow, k, s, p,
                        (const float*)gy.data, gy.stride[0], gy.stride[2], gy.stride[3], argmax, (float*)dx.data,
                        dx.stride[0], dx.stride[2], dx.stride[3]);
-  return (int)hipGetLastError();
+  return launched("maxpool2d_bwd");
 }
 
 extern "C" int32_t tpg_avgpool_fwd(int32_t n, int32_t c, int32_t h, int32_t w, tpg_tensor x, tpg_tensor y,
                                    tpg_stream_t stream) {
-  if (!x.data || !y.data) return ffail(-10, "avgpool: NULL tensor");
-  if (x.dtype != y.dtype || x.stride[1] != 1 || y.stride[1] != 1) return ffail(-12, "avgpool: channels-last");
+  if (int32_t grc = group_sync()) return grc;
+  if (!x.data || !y.data) return fail(-10, "avgpool: NULL tensor");
+  if (x.dtype != y.dtype || x.stride[1] != 1 || y.stride[1] != 1) return fail(-12, "avgpool: channels-last");
   hipStream_t st = (hipStream_t)stream;
   const int grid = (n * c + 255) / 256;
   if (x.dtype == TPG_F16)
@@ -687,13 +691,14 @@ extern "C" int32_t tpg_avgpool_fwd(int32_t n, int32_t c, int32_t h, int32_t w, t
   else
     hipLaunchKernelGGL(avgpool_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, n, c, h, w, (const float*)x.data,
                        x.stride[0], x.stride[2], x.stride[3], (float*)y.data, y.stride[0]);
-  return (int)hipGetLastError();
+  return launched("avgpool_fwd");
 }
 
 extern "C" int32_t tpg_avgpool_bwd(int32_t n, int32_t c, int32_t h, int32_t w, tpg_tensor gy, tpg_tensor dx,
                                    tpg_stream_t stream) {
-  if (!gy.data || !dx.data) return ffail(-10, "avgpool bwd: NULL tensor");
-  if (gy.dtype != dx.dtype || gy.stride[1] != 1 || dx.stride[1] != 1) return ffail(-12, "avgpool: channels-last");
+  if (int32_t grc = group_sync()) return grc;
+  if (!gy.data || !dx.data) return fail(-10, "avgpool bwd: NULL tensor");
+  if (gy.dtype != dx.dtype || gy.stride[1] != 1 || dx.stride[1] != 1) return fail(-12, "avgpool: channels-last");
   hipStream_t st = (hipStream_t)stream;
   const int grid = grid_cap((int64_t)n * h * w * c);
   if (gy.dtype == TPG_F16)
@@ -705,18 +710,19 @@ extern "C" int32_t tpg_avgpool_bwd(int32_t n, int32_t c, int32_t h, int32_t w, t
   else
     hipLaunchKernelGGL(avgpool_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, n, c, h, w, (const float*)gy.data,
                        gy.stride[0], (float*)dx.data, dx.stride[0], dx.stride[2], dx.stride[3]);
-  return (int)hipGetLastError();
+  return launched("avgpool_bwd");
 }
 
 extern "C" int32_t tpg_bn_fold(int32_t cout, int32_t cin, int32_t kh, int32_t kw, tpg_tensor w, const float* bias,
                                const float* gamma, const float* beta, const float* mean, const float* var, float eps,
                                tpg_tensor w_out, float* b_out, tpg_stream_t stream) {
-  if (!w.data || !w_out.data || !b_out || !gamma || !beta || !mean || !var) return ffail(-10, "bn_fold: NULL");
-  if (w.dtype != TPG_F32 || w_out.dtype != TPG_F32) return ffail(-13, "bn_fold: weights must be fp32");
+  if (int32_t grc = group_sync()) return grc;
+  if (!w.data || !w_out.data || !b_out || !gamma || !beta || !mean || !var) return fail(-10, "bn_fold: NULL");
+  if (w.dtype != TPG_F32 || w_out.dtype != TPG_F32) return fail(-13, "bn_fold: weights must be fp32");
   const int grid = grid_cap((int64_t)cout * cin * kh * kw);
   hipLaunchKernelGGL(bn_fold_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, cout, cin, kh, kw, w, bias, gamma,
                      beta, mean, var, eps, w_out, b_out);
-  return (int)hipGetLastError();
+  return launched("bn_fold");
 }
 
 // ---------------------------------------------------------- BatchNorm2d training --
@@ -767,10 +773,11 @@ extern "C" int32_t tpg_bn_train_fwd(int32_t n, int32_t c, int32_t h, int32_t w, 
                                     const float* beta, float* running_mean, float* running_var, float momentum,
                                     float eps, int32_t act, float slope, tpg_tensor y, float* save_mean,
                                     float* save_invstd, float* ws, tpg_stream_t stream) {
-  if (!x.data || !y.data || !gamma || !beta || !save_mean || !save_invstd || !ws) return ffail(-10, "bn_train_fwd: NULL");
-  if ((running_mean == nullptr) != (running_var == nullptr)) return ffail(-10, "bn_train_fwd: running stats pair");
+  if (int32_t grc = group_sync()) return grc;
+  if (!x.data || !y.data || !gamma || !beta || !save_mean || !save_invstd || !ws) return fail(-10, "bn_train_fwd: NULL");
+  if ((running_mean == nullptr) != (running_var == nullptr)) return fail(-10, "bn_train_fwd: running stats pair");
   if (!pix_dense(x, h, w, c, x.dtype) || !pix_dense(y, h, w, c, x.dtype))
-    return ffail(-12, "bn_train: pixel-dense 16-byte aligned channels-last tensors");
+    return fail(-12, "bn_train: pixel-dense 16-byte aligned channels-last tensors");
   BnArgs a;
   memset(&a, 0, sizeof(a));
   a.npix = (int64_t)n * h * w; a.C = c; a.act = act; a.slope = slope; a.eps = eps; a.momentum = momentum;
@@ -778,20 +785,24 @@ extern "C" int32_t tpg_bn_train_fwd(int32_t n, int32_t c, int32_t h, int32_t w, 
   a.gamma = gamma; a.beta = beta; a.acc = ws; a.mean = save_mean; a.invstd = save_invstd;
   a.running_mean = running_mean; a.running_var = running_var;
   hipStream_t s = (hipStream_t)stream;
-  if (hipError_t e = hipMemsetAsync(ws, 0, sizeof(float) * 2 * c, s)) return (int)e;
+  if (hipError_t e = hipMemsetAsync(ws, 0, sizeof(float) * 2 * c, s)) return hip_check((int)e, "bn_train_fwd");
   const int blocks = bn_blocks(a);
-  return x.dtype == TPG_F16 ? bn_launch_fwd<_Float16>(a, blocks, s) : x.dtype == TPG_BF16 ? bn_launch_fwd<__bf16>(a, blocks, s) : bn_launch_fwd<float>(a, blocks, s);
+  return hip_check(x.dtype == TPG_F16    ? bn_launch_fwd<_Float16>(a, blocks, s)
+                   : x.dtype == TPG_BF16 ? bn_launch_fwd<__bf16>(a, blocks, s)
+                                         : bn_launch_fwd<float>(a, blocks, s),
+                   "bn_train_fwd");
 }
 
 extern "C" int32_t tpg_bn_train_bwd(int32_t n, int32_t c, int32_t h, int32_t w, int32_t act, float slope,
                                     tpg_tensor dy, tpg_tensor y, tpg_tensor x, const float* gamma,
                                     const float* save_mean, const float* save_invstd, tpg_tensor dx, float* dgamma,
                                     float* dbeta, float* ws, tpg_stream_t stream) {
-  if (!dy.data || !y.data || !x.data || !gamma || !save_mean || !save_invstd || !ws) return ffail(-10, "bn_train_bwd: NULL");
+  if (int32_t grc = group_sync()) return grc;
+  if (!dy.data || !y.data || !x.data || !gamma || !save_mean || !save_invstd || !ws) return fail(-10, "bn_train_bwd: NULL");
   const int dt = x.dtype;
   if (!pix_dense(x, h, w, c, dt) || !pix_dense(y, h, w, c, dt) || !pix_dense(dy, h, w, c, dt) ||
       (dx.data && !pix_dense(dx, h, w, c, dt)))
-    return ffail(-12, "bn_train: pixel-dense 16-byte aligned channels-last tensors");
+    return fail(-12, "bn_train: pixel-dense 16-byte aligned channels-last tensors");
   BnArgs a;
   memset(&a, 0, sizeof(a));
   a.npix = (int64_t)n * h * w; a.C = c; a.act = act; a.slope = slope;
@@ -800,7 +811,10 @@ extern "C" int32_t tpg_bn_train_bwd(int32_t n, int32_t c, int32_t h, int32_t w, 
   a.gamma = gamma; a.acc = ws; a.mean = const_cast<float*>(save_mean); a.invstd = const_cast<float*>(save_invstd);
   a.dgamma = dgamma; a.dbeta = dbeta;
   hipStream_t s = (hipStream_t)stream;
-  if (hipError_t e = hipMemsetAsync(ws, 0, sizeof(float) * 2 * c, s)) return (int)e;
+  if (hipError_t e = hipMemsetAsync(ws, 0, sizeof(float) * 2 * c, s)) return hip_check((int)e, "bn_train_bwd");
   const int blocks = bn_blocks(a);
-  return dt == TPG_F16 ? bn_launch_bwd<_Float16>(a, blocks, s) : dt == TPG_BF16 ? bn_launch_bwd<__bf16>(a, blocks, s) : bn_launch_bwd<float>(a, blocks, s);
+  return hip_check(dt == TPG_F16    ? bn_launch_bwd<_Float16>(a, blocks, s)
+                   : dt == TPG_BF16 ? bn_launch_bwd<__bf16>(a, blocks, s)
+                                    : bn_launch_bwd<float>(a, blocks, s),
+                   "bn_train_bwd");
 }

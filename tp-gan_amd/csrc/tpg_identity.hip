@@ -304,19 +304,11 @@ struct TopkPlan {
 };
 
 int topk_plan(const char* fn, int32_t P, int32_t G, int32_t k, int32_t gchunk, TopkPlan* out) {
-  static thread_local char msg[160];
-  if (P < 0 || P > ID_MAXROWS || G < 0 || G > ID_MAXROWS) {
-    snprintf(msg, sizeof msg, "%s: P and G must be in 0..2^24, got %d and %d", fn, P, G);
-    return record_error(-2, msg);
-  }
-  if (k < 1 || k > CT_SLOTS) {
-    snprintf(msg, sizeof msg, "%s: k must be in 1..8, got %d", fn, k);
-    return record_error(-2, msg);
-  }
-  if (gchunk < 0 || (gchunk >= 1 && gchunk <= 15)) {
-    snprintf(msg, sizeof msg, "%s: gchunk must be 0 (automatic) or >= 16, got %d", fn, gchunk);
-    return record_error(-2, msg);
-  }
+  if (P < 0 || P > ID_MAXROWS || G < 0 || G > ID_MAXROWS)
+    return fail(-2, "%s: P and G must be in 0..2^24, got %d and %d", fn, P, G);
+  if (k < 1 || k > CT_SLOTS) return fail(-2, "%s: k must be in 1..8, got %d", fn, k);
+  if (gchunk < 0 || (gchunk >= 1 && gchunk <= 15))
+    return fail(-2, "%s: gchunk must be 0 (automatic) or >= 16, got %d", fn, gchunk);
   const int64_t ptiles = P > 0 ? ((int64_t)P + CT_ROWS - 1) / CT_ROWS : 1;
   int64_t chunk = gchunk;
   if (gchunk == 0) {
@@ -327,10 +319,8 @@ int topk_plan(const char* fn, int32_t P, int32_t G, int32_t k, int32_t gchunk, T
     chunk = (tiles + want - 1) / want * CT_ROWS;
   }
   const int64_t nchunks = ((int64_t)G + chunk - 1) / chunk;
-  if (ptiles * nchunks > 0x7fffffffLL) {
-    snprintf(msg, sizeof msg, "%s: too many blocks (probe tiles x chunks >= 2^31); raise gchunk", fn);
-    return record_error(-2, msg);
-  }
+  if (ptiles * nchunks > 0x7fffffffLL)
+    return fail(-2, "%s: too many blocks (probe tiles x chunks >= 2^31); raise gchunk", fn);
   out->chunk = chunk;
   out->nchunks = (int32_t)nchunks;
   out->ptiles = (int32_t)ptiles;
@@ -340,24 +330,12 @@ int topk_plan(const char* fn, int32_t P, int32_t G, int32_t k, int32_t gchunk, T
 }
 
 int rows_check(const char* fn, int32_t n, int32_t d) {
-  static thread_local char msg[160];
-  if (n < 0 || n > ID_MAXROWS) {
-    snprintf(msg, sizeof msg, "%s: n must be in 0..2^24, got %d", fn, n);
-    return record_error(-2, msg);
-  }
-  if (d < 1 || d > ID_MAXD) {
-    snprintf(msg, sizeof msg, "%s: d must be in 1..4096, got %d", fn, d);
-    return record_error(-2, msg);
-  }
+  if (n < 0 || n > ID_MAXROWS) return fail(-2, "%s: n must be in 0..2^24, got %d", fn, n);
+  if (d < 1 || d > ID_MAXD) return fail(-2, "%s: d must be in 1..4096, got %d", fn, d);
   return 0;
 }
 
 bool dtype_ok(int32_t dt) { return dt == TPG_F32 || dt == TPG_BF16 || dt == TPG_F16; }
-
-int launch_status(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : record_error((int)e, hipGetErrorString(e));
-}
 
 template <typename EA>
 void launch_pairs(int32_t bdt, const PairArgs& p, dim3 grid, hipStream_t st) {
@@ -373,12 +351,13 @@ using namespace tpg;
 
 extern "C" int32_t tpg_l2_normalize(int32_t n, int32_t d, tpg_tensor x, float* out, int32_t dpad, float* norm,
                                     int32_t* status, tpg_stream_t stream) {
+  if (int32_t grc = group_sync()) return grc;
   const int rc = rows_check("l2_normalize", n, d);
   if (rc) return rc;
-  if (dpad != (d + 3) / 4 * 4) return record_error(-2, "l2_normalize: dpad must be d rounded up to a multiple of 4");
-  if (!dtype_ok(x.dtype)) return record_error(-3, "l2_normalize: bad dtype");
+  if (dpad != (d + 3) / 4 * 4) return fail(-2, "l2_normalize: dpad must be d rounded up to a multiple of 4");
+  if (!dtype_ok(x.dtype)) return fail(-3, "l2_normalize: bad dtype");
   if (n == 0) return 0;
-  if (!x.data || !out || !status) return record_error(-10, "l2_normalize: NULL pointer");
+  if (!x.data || !out || !status) return fail(-10, "l2_normalize: NULL pointer");
   NormArgs a;
   a.x = x.data;
   a.s0 = x.stride[0];
@@ -394,16 +373,17 @@ extern "C" int32_t tpg_l2_normalize(int32_t n, int32_t d, tpg_tensor x, float* o
   if (x.dtype == TPG_F32) hipLaunchKernelGGL(l2_normalize_kernel<float>, grid, dim3(256), 0, st, a);
   else if (x.dtype == TPG_BF16) hipLaunchKernelGGL(l2_normalize_kernel<__bf16>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(l2_normalize_kernel<_Float16>, grid, dim3(256), 0, st, a);
-  return launch_status("l2_normalize");
+  return launched("l2_normalize");
 }
 
 extern "C" int32_t tpg_cosine_pairs(int32_t n, int32_t d, tpg_tensor a, tpg_tensor b, float* cos, int32_t* status,
                                     tpg_stream_t stream) {
+  if (int32_t grc = group_sync()) return grc;
   const int rc = rows_check("cosine_pairs", n, d);
   if (rc) return rc;
-  if (!dtype_ok(a.dtype) || !dtype_ok(b.dtype)) return record_error(-3, "cosine_pairs: bad dtype");
+  if (!dtype_ok(a.dtype) || !dtype_ok(b.dtype)) return fail(-3, "cosine_pairs: bad dtype");
   if (n == 0) return 0;
-  if (!a.data || !b.data || !cos || !status) return record_error(-10, "cosine_pairs: NULL pointer");
+  if (!a.data || !b.data || !cos || !status) return fail(-10, "cosine_pairs: NULL pointer");
   PairArgs p;
   p.a = a.data;
   p.b = b.data;
@@ -420,7 +400,7 @@ extern "C" int32_t tpg_cosine_pairs(int32_t n, int32_t d, tpg_tensor a, tpg_tens
   if (a.dtype == TPG_F32) launch_pairs<float>(b.dtype, p, grid, st);
   else if (a.dtype == TPG_BF16) launch_pairs<__bf16>(b.dtype, p, grid, st);
   else launch_pairs<_Float16>(b.dtype, p, grid, st);
-  return launch_status("cosine_pairs");
+  return launched("cosine_pairs");
 }
 
 extern "C" int64_t tpg_cosine_topk_workspace(int32_t P, int32_t G, int32_t k, int32_t gchunk) {
@@ -432,17 +412,18 @@ extern "C" int64_t tpg_cosine_topk_workspace(int32_t P, int32_t G, int32_t k, in
 extern "C" int32_t tpg_cosine_topk(int32_t P, int32_t G, int32_t d, int32_t dpad, const float* probes,
                                    const float* gallery, int32_t k, const int32_t* skip, int32_t gchunk, int32_t* idx,
                                    float* score, void* ws, size_t ws_bytes, tpg_stream_t stream) {
+  if (int32_t grc = group_sync()) return grc;
   TopkPlan pl;
   int rc = topk_plan("cosine_topk", P, G, k, gchunk, &pl);
   if (rc) return rc;
-  if (d < 1 || d > ID_MAXD) return record_error(-2, "cosine_topk: d must be in 1..4096");
-  if (dpad != (d + 3) / 4 * 4) return record_error(-2, "cosine_topk: dpad must be d rounded up to a multiple of 4");
+  if (d < 1 || d > ID_MAXD) return fail(-2, "cosine_topk: d must be in 1..4096");
+  if (dpad != (d + 3) / 4 * 4) return fail(-2, "cosine_topk: dpad must be d rounded up to a multiple of 4");
   if (P == 0) return 0;
-  if (!probes || (G > 0 && !gallery) || !idx || !score || !ws) return record_error(-10, "cosine_topk: NULL pointer");
+  if (!probes || (G > 0 && !gallery) || !idx || !score || !ws) return fail(-10, "cosine_topk: NULL pointer");
   if ((uintptr_t)probes % 16 != 0 || (uintptr_t)gallery % 16 != 0 || (uintptr_t)ws % 8 != 0)
-    return record_error(-4, "cosine_topk: probes and gallery must be 16-byte aligned, the workspace 8-byte aligned");
+    return fail(-4, "cosine_topk: probes and gallery must be 16-byte aligned, the workspace 8-byte aligned");
   if ((int64_t)ws_bytes < pl.ws_bytes)
-    return record_error(-4, "cosine_topk: workspace too small (tpg_cosine_topk_workspace)");
+    return fail(-4, "cosine_topk: workspace too small (tpg_cosine_topk_workspace)");
   TopkArgs a;
   a.probes = probes;
   a.gallery = gallery;
@@ -461,9 +442,9 @@ extern "C" int32_t tpg_cosine_topk(int32_t P, int32_t G, int32_t d, int32_t dpad
   hipStream_t st = (hipStream_t)stream;
   if (pl.nchunks > 0) {
     hipLaunchKernelGGL(cosine_topk_kernel, dim3((unsigned)((int64_t)pl.ptiles * pl.nchunks)), dim3(256), 0, st, a);
-    rc = launch_status("cosine_topk");
+    rc = launched("cosine_topk");
     if (rc) return rc;
   }
   hipLaunchKernelGGL(cosine_merge_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, a);
-  return launch_status("cosine_topk");
+  return launched("cosine_topk");
 }

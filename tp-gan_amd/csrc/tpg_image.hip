@@ -309,21 +309,12 @@ __global__ __launch_bounds__(64) void metrics_final_kernel(const TilePartial* pa
 }
 
 int metrics_check(const char* fn, int32_t n, int32_t h, int32_t w, int32_t c, int64_t* tiles_x, int64_t* tiles) {
-  static thread_local char msg[160];
-  if (n < 0 || h <= 0 || w <= 0 || h > 32768 || w > 32768) {
-    snprintf(msg, sizeof msg, "%s: bad sizes (n >= 0, sides in 1..32768)", fn);
-    return record_error(-2, msg);
-  }
-  if (c < 1 || c > 4) {
-    snprintf(msg, sizeof msg, "%s: c must be in 1..4, got %d", fn, c);
-    return record_error(-2, msg);
-  }
+  if (n < 0 || h <= 0 || w <= 0 || h > 32768 || w > 32768)
+    return fail(-2, "%s: bad sizes (n >= 0, sides in 1..32768)", fn);
+  if (c < 1 || c > 4) return fail(-2, "%s: c must be in 1..4, got %d", fn, c);
   *tiles_x = (w + MT - 1) / MT;
   *tiles = *tiles_x * ((h + MT - 1) / MT);
-  if ((int64_t)n * *tiles > 0x7fffffffLL) {
-    snprintf(msg, sizeof msg, "%s: batch too large (n * tiles >= 2^31)", fn);
-    return record_error(-2, msg);
-  }
+  if ((int64_t)n * *tiles > 0x7fffffffLL) return fail(-2, "%s: batch too large (n * tiles >= 2^31)", fn);
   return 0;
 }
 
@@ -334,11 +325,12 @@ using namespace tpg;
 
 extern "C" int32_t tpg_denorm_u8(int32_t n, int32_t c, int32_t h, int32_t w, tpg_tensor x, uint8_t* out,
                                  tpg_stream_t stream) {
-  if (n < 0 || h <= 0 || w <= 0) return record_error(-2, "denorm_u8: bad sizes");
-  if (c < 1 || c > 4) return record_error(-2, "denorm_u8: c must be in 1..4");
-  if (x.dtype != TPG_F32 && x.dtype != TPG_BF16 && x.dtype != TPG_F16) return record_error(-3, "denorm_u8: bad dtype");
+  if (int32_t grc = group_sync()) return grc;
+  if (n < 0 || h <= 0 || w <= 0) return fail(-2, "denorm_u8: bad sizes");
+  if (c < 1 || c > 4) return fail(-2, "denorm_u8: c must be in 1..4");
+  if (x.dtype != TPG_F32 && x.dtype != TPG_BF16 && x.dtype != TPG_F16) return fail(-3, "denorm_u8: bad dtype");
   if (n == 0) return 0;
-  if (!x.data || !out) return record_error(-10, "denorm_u8: NULL pointer");
+  if (!x.data || !out) return fail(-10, "denorm_u8: NULL pointer");
   DenormArgs a;
   a.x = x.data;
   for (int i = 0; i < 4; ++i) a.s[i] = x.stride[i];
@@ -346,7 +338,7 @@ extern "C" int32_t tpg_denorm_u8(int32_t n, int32_t c, int32_t h, int32_t w, tpg
   a.npix = (int64_t)n * h * w;
   a.h = h;
   a.w = w;
-  if ((a.npix + 3) / 4 / 256 >= 0x7fffffffLL) return record_error(-2, "denorm_u8: batch too large");
+  if ((a.npix + 3) / 4 / 256 >= 0x7fffffffLL) return fail(-2, "denorm_u8: batch too large");
   const int es = x.dtype == TPG_F32 ? 4 : 2;
   const uintptr_t addr = (uintptr_t)x.data;
   auto mult = [&](int k) {  // base address and the batch / row / pixel strides k-element aligned
@@ -362,8 +354,7 @@ extern "C" int32_t tpg_denorm_u8(int32_t n, int32_t c, int32_t h, int32_t w, tpg
   if (x.dtype == TPG_F32) launch_denorm<float>(c, a, st);
   else if (x.dtype == TPG_BF16) launch_denorm<__bf16>(c, a, st);
   else launch_denorm<_Float16>(c, a, st);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : record_error((int)e, hipGetErrorString(e));
+  return launched("denorm_u8");
 }
 
 extern "C" int64_t tpg_image_metrics_workspace(int32_t n, int32_t h, int32_t w, int32_t c) {
@@ -376,15 +367,16 @@ extern "C" int64_t tpg_image_metrics_workspace(int32_t n, int32_t h, int32_t w, 
 extern "C" int32_t tpg_image_metrics_u8(int32_t n, int32_t h, int32_t w, int32_t c, const uint8_t* a,
                                         const uint8_t* b, int64_t* sse, float* ssim, void* ws, size_t ws_bytes,
                                         tpg_stream_t stream) {
+  if (int32_t grc = group_sync()) return grc;
   int64_t tx, tiles;
   const int rc = metrics_check("image_metrics_u8", n, h, w, c, &tx, &tiles);
   if (rc) return rc;
-  if (ssim && (h < MW || w < MW)) return record_error(-2, "image_metrics_u8: SSIM needs h and w >= 11");
+  if (ssim && (h < MW || w < MW)) return fail(-2, "image_metrics_u8: SSIM needs h and w >= 11");
   if (n == 0) return 0;
-  if (!a || !b || !sse || !ws) return record_error(-10, "image_metrics_u8: NULL pointer");
-  if ((uintptr_t)ws % 8 != 0) return record_error(-4, "image_metrics_u8: workspace must be 8-byte aligned");
+  if (!a || !b || !sse || !ws) return fail(-10, "image_metrics_u8: NULL pointer");
+  if ((uintptr_t)ws % 8 != 0) return fail(-4, "image_metrics_u8: workspace must be 8-byte aligned");
   if (ws_bytes < sizeof(TilePartial) * (size_t)n * (size_t)tiles)
-    return record_error(-4, "image_metrics_u8: workspace too small (tpg_image_metrics_workspace)");
+    return fail(-4, "image_metrics_u8: workspace too small (tpg_image_metrics_workspace)");
   MetricsArgs m;
   m.a = a;
   m.b = b;
@@ -403,11 +395,9 @@ extern "C" int32_t tpg_image_metrics_u8(int32_t n, int32_t h, int32_t w, int32_t
   hipStream_t st = (hipStream_t)stream;
   TilePartial* part = reinterpret_cast<TilePartial*>(ws);
   hipLaunchKernelGGL(metrics_tile_kernel, dim3((unsigned)(n * tiles)), dim3(M_THREADS), 0, st, m, part);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return record_error((int)e, hipGetErrorString(e));
+  if (int32_t e = launched("image_metrics_u8")) return e;
   const double count = ssim ? (double)c * (h - MW + 1) * (double)(w - MW + 1) : 1.0;
   hipLaunchKernelGGL(metrics_final_kernel, dim3((unsigned)n), dim3(64), 0, st, (const TilePartial*)part, (int)tiles,
                      count, sse, ssim);
-  e = hipGetLastError();
-  return e == hipSuccess ? 0 : record_error((int)e, hipGetErrorString(e));
+  return launched("image_metrics_u8");
 }

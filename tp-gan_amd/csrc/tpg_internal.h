@@ -1,5 +1,5 @@
 // Internal kernel interfaces of libtpgan_hip.so (gfx950).  The public C-ABI is
-// include/tpgan.h; tpg_capi.hip turns a tpg_conv_desc into the problems below.
+// include/tpgan.h; the planners (tpg_plan.h) turn a tpg_conv_desc into the problems below.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -511,34 +511,64 @@ int act_vec_args(int n, int c, int h, int w, int act, float slope, const ::tpg_t
 int launch_act_vec(const ActVecArgs& a, int dtype, hipStream_t s);
 int launch_act_vec_group(const ActVecArgs* a, int n, int dtype, hipStream_t s);
 
-// sets the thread-local message returned by tpg_last_error() (tpg_capi.hip); returns code
-int record_error(int code, const char* msg);
+// ---------------------------------------------------------------- errors (tpg_error.hip) ----
+// Every extern "C" entry point returns through one of these; each sets the thread-local message
+// of tpg_last_error() and returns the code.  fail: a rejected call (printf format); hip_check: 0,
+// or "<what> failed: <hip error string>" for a launcher's status e (hipError_t as int; < 0: no
+// kernel for the config, code -100); launched: hip_check of hipGetLastError(), the end of an
+// entry point that launched its kernels itself.
+int32_t fail(int32_t code, const char* fmt, ...);
+int32_t hip_check(int e, const char* what);
+int32_t launched(const char* what);
 
 // tpg_set_deterministic(): every reduction in a fixed order (no split-K / pixel-split fp32
 // atomics, one block per bias-gradient sum); process-wide, for parity and run-to-run tests
 int deterministic();
 
-// launchers (return hipError_t as int); cfg selects the tile shape
-int launch_igemm(const IgemmArgs& a, int dtype, int cfg, hipStream_t s);
+// ---------------------------------------------------------------- launch groups (tpg_group.hip) ----
+// Every extern "C" entry point that launches calls group_sync() before its first launch: the
+// launches recorded by an open group run first (one by one, in order), so the semantics are those
+// of the calls run in order.  Returns a status already passed through hip_check.
+int32_t group_sync();
+// the four groupable kernels: recorded into an open group, launched otherwise (a launcher's status)
+int do_halo(const HaloArgs& h, int dtype, int cfg, hipStream_t s, bool mask);
+int do_epilogue(const EpiArgs& e, hipStream_t s);
+int do_wgrad2(const Wgrad2Args& w, int dtype, int cfg, int bm, int bn, hipStream_t s);
+int do_act_bwd(int n, int c, int h, int w, int act, float slope, const ::tpg_tensor& gy, const ::tpg_tensor& y,
+               const ::tpg_tensor& g, float* dbias, hipStream_t s);
+
+// ---------------------------------------------------------------- host predicates of the planners ----
+// All the planner units (tpg_plan_data.hip, tpg_plan_wgrad.hip) call from the kernel files: tile
+// shapes, config ids and what a launcher would refuse (-1), so that a finished plan never meets the
+// refusal (pw_accepts reads A's geometry and strides from a).  No launch, no HIP call.
 int igemm_cfg_bn(int cfg);
 int igemm_cfg_bm(int cfg);
-int launch_wgrad(const WgradArgs& a, int dtype, int cfg, hipStream_t s);
+int halo_cfg(int hl, int bn);
+int halo_cfg512(int bn);
+bool halo_accepts(const HaloArgs& a, int cfg, bool mask);
+bool pw_accepts(const HaloArgs& a, int dtype);
+int pw_tile_bm(int cfg);
+int pw_tile_bn(int cfg);
+size_t halo_wp_bytes(int nks, int ntaps, int bn, int ntiles, int half);
+// pipeline steps of a halo problem (= weight slices of its packed image): ntaps per k-step, the
+// last k-step paired (ceil(ntaps / 2)) when half
+__host__ __device__ inline int halo_steps(int nks, int ntaps, int half) {
+  return half ? (nks - 1) * ntaps + (ntaps + 1) / 2 : nks * ntaps;
+}
+int wgrad_rh_tile(int cfg, int* bm, int* bc);
 int wgrad_cfg_bm(int cfg);
 int wgrad_cfg_bn(int cfg);
-int launch_pack(const PackArgs& a, hipStream_t s);
 int wgrad2_cfg(int bm, int bn);
+
+// launchers (return hipError_t as int); cfg selects the tile shape
+int launch_igemm(const IgemmArgs& a, int dtype, int cfg, hipStream_t s);
+int launch_wgrad(const WgradArgs& a, int dtype, int cfg, hipStream_t s);
+int launch_pack(const PackArgs& a, hipStream_t s);
 int launch_wgrad2(const Wgrad2Args& a, int dtype, int cfg, int bm, int bn, hipStream_t s);
 int launch_epilogue(const EpiArgs& a, hipStream_t s);
 int launch_wgrad_rh(const WgradRHArgs& a, hipStream_t s);
-int wgrad_rh_tile(int cfg, int* bm, int* bc);
-int halo_cfg(int hl, int bn);
 size_t halo_lds_bytes(int hcap, int bn, int rs = 3, int bm = 256);
-int halo_cfg512(int bn);
 int launch_halo(const HaloArgs& a, int dtype, int cfg, hipStream_t s, bool mask = false);
-// what launch_halo / launch_pw refuse (-1), as host predicates: the planner calls them so that a
-// finished plan never meets the refusal (pw_accepts reads A's geometry and strides from a)
-bool halo_accepts(const HaloArgs& a, int cfg, bool mask);
-bool pw_accepts(const HaloArgs& a, int dtype);
 // pointwise (1x1) GEMM kernel on a one-tap halo plan (a.pw = tile config 1..4: 128x128, 128x64,
 // 64x128, 64x64 rows x output channels); same packed weights, epilogue and split-K slices
 int launch_pw(const HaloArgs& a, int dtype, hipStream_t s);
@@ -557,14 +587,28 @@ int launch_ssd_loss_bwd(int B, int n, int C, const float* pred, const float* cls
                         const float* terms, const float* gout, float* dloc, float* dcls, hipStream_t s);
 int launch_ssd_decode(int B, int n, int C, const float* loc, const float* cls, float conf, float nms_thr, int top_k,
                       int* keep, float* score, hipStream_t s);
-int pw_tile_bm(int cfg);
-int pw_tile_bn(int cfg);
 int launch_pack_halo(const PackArgs& a, int nks, int bn, int ntiles, hipStream_t s);
-// pipeline steps of a halo problem (= weight slices of its packed image): ntaps per k-step, the
-// last k-step paired (ceil(ntaps / 2)) when half
-__host__ __device__ inline int halo_steps(int nks, int ntaps, int half) {
-  return half ? (nks - 1) * ntaps + (ntaps + 1) / 2 : nks * ntaps;
-}
-size_t halo_wp_bytes(int nks, int ntaps, int bn, int ntiles, int half);
+// elementwise launchers behind the C entry points of the same names (tpg_elementwise.hip);
+// launch_adam / launch_grad_check: -1 for misaligned buffers, before any launch
+int launch_act_bwd(int32_t n, int32_t c, int32_t h, int32_t w, int32_t act, float slope, ::tpg_tensor gy, ::tpg_tensor y,
+                   ::tpg_tensor g, float* dbias, hipStream_t s);
+int launch_colsum(int32_t n, int32_t c, int32_t h, int32_t w, ::tpg_tensor g, float* dbias, hipStream_t s);
+int launch_copy4d(int32_t n, int32_t c, int32_t h, int32_t w, ::tpg_tensor in, ::tpg_tensor out, hipStream_t s);
+int launch_fold_taps(int32_t n, int32_t c, int32_t h, int32_t w, int32_t fh, int32_t fw, int32_t sh, int32_t sw,
+                     int32_t pt, int32_t pl, int32_t oh, int32_t ow, ::tpg_tensor x, ::tpg_tensor y, int32_t backward,
+                     hipStream_t s);
+int launch_fuse_fwd(int32_t n, int32_t c, int32_t oh, int32_t ow, const ::tpg_tensor* parts, const int32_t* ph,
+                    const int32_t* pw, const int32_t* top, const int32_t* left, ::tpg_tensor y, uint8_t* amax,
+                    hipStream_t s);
+int launch_fuse_bwd(int32_t n, int32_t c, int32_t oh, int32_t ow, ::tpg_tensor gy, const uint8_t* amax,
+                    const ::tpg_tensor* dparts, const int32_t* ph, const int32_t* pw, const int32_t* top,
+                    const int32_t* left, hipStream_t s);
+int launch_maxout_fwd(int32_t b, int32_t m, ::tpg_tensor x, ::tpg_tensor y, uint8_t* amax, hipStream_t s);
+int launch_maxout_bwd(int32_t b, int32_t m, ::tpg_tensor gy, const uint8_t* amax, ::tpg_tensor dx, hipStream_t s);
+int launch_adam(int64_t numel, float* param, const float* grad, float* m, float* v, float lr, float b1, float b2,
+                float eps, float wd, int32_t host_step, float gscale, float* state, hipStream_t s);
+int launch_grad_check(int64_t numel, const float* grad, float* state, hipStream_t s);
+int launch_reflect_fold(int N, int C, int H, int W, int pt, int pb, int pl, int pr, const ::tpg_tensor& dpad,
+                        const ::tpg_tensor& dx, hipStream_t s);
 
 }  // namespace tpg

@@ -195,7 +195,7 @@ using namespace tpg;
 
 extern "C" int32_t tpg_resize_ksize(int32_t in_size, int32_t out_size) {
   if (!size_ok(in_size) || !size_ok(out_size)) {
-    record_error(-2, "resize_ksize: sizes must be in 1..4096");
+    fail(-2, "resize_ksize: sizes must be in 1..4096");
     return 0;
   }
   return ksize_of(in_size, out_size);
@@ -203,7 +203,7 @@ extern "C" int32_t tpg_resize_ksize(int32_t in_size, int32_t out_size) {
 
 extern "C" int64_t tpg_resize_table_ints(int32_t in_size, int32_t out_size) {
   if (!size_ok(in_size) || !size_ok(out_size)) {
-    record_error(-2, "resize_table_ints: sizes must be in 1..4096");
+    fail(-2, "resize_table_ints: sizes must be in 1..4096");
     return 0;
   }
   return (int64_t)out_size * (2 + ksize_of(in_size, out_size));
@@ -211,8 +211,8 @@ extern "C" int64_t tpg_resize_table_ints(int32_t in_size, int32_t out_size) {
 
 extern "C" int32_t tpg_resize_coeffs(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* coeffs) {
 #pragma clang fp contract(off)
-  if (!size_ok(in_size) || !size_ok(out_size)) return record_error(-2, "resize_coeffs: sizes must be in 1..4096");
-  if (!bounds || !coeffs) return record_error(-10, "resize_coeffs: NULL pointer");
+  if (!size_ok(in_size) || !size_ok(out_size)) return fail(-2, "resize_coeffs: sizes must be in 1..4096");
+  if (!bounds || !coeffs) return fail(-10, "resize_coeffs: NULL pointer");
   const double scale = (double)in_size / (double)out_size;
   const double fs = scale < 1.0 ? 1.0 : scale;
   const double support = 3.0 * fs;
@@ -226,7 +226,7 @@ extern "C" int32_t tpg_resize_coeffs(int32_t in_size, int32_t out_size, int32_t*
     int xmax = (int)(center + support + 0.5);
     if (xmax > in_size) xmax = in_size;
     const int n = xmax - xmin;
-    if (n < 0 || n > ksize) return record_error(-2, "resize_coeffs: window outside the table");
+    if (n < 0 || n > ksize) return fail(-2, "resize_coeffs: window outside the table");
     double tot = 0.0;
     for (int x = 0; x < n; ++x) {
       w[x] = lanczos_filter((x + xmin - center + 0.5) * ss);
@@ -237,7 +237,7 @@ extern "C" int32_t tpg_resize_coeffs(int32_t in_size, int32_t out_size, int32_t*
       const double v = tot != 0.0 ? w[x] / tot : w[x];
       const double f = v < 0 ? v * (double)(1 << RS_PB) - 0.5 : v * (double)(1 << RS_PB) + 0.5;
       // the kernels multiply with the 24-bit multiply-add
-      if (!(f > -8388608.0 && f < 8388608.0)) return record_error(-2, "resize_coeffs: coefficient exceeds 24 bits");
+      if (!(f > -8388608.0 && f < 8388608.0)) return fail(-2, "resize_coeffs: coefficient exceeds 24 bits");
       k[x] = (int32_t)f;
     }
     for (int x = n; x < ksize; ++x) k[x] = 0;
@@ -251,7 +251,7 @@ extern "C" size_t tpg_resize_job_bytes(void) { return sizeof(ResizeJob); }
 
 extern "C" int64_t tpg_resize_workspace(int32_t h, int32_t w, int32_t out_h, int32_t out_w) {
   if (!size_ok(h) || !size_ok(w) || !size_ok(out_h) || !size_ok(out_w))
-    return record_error(-2, "resize_workspace: sizes must be in 1..4096");
+    return fail(-2, "resize_workspace: sizes must be in 1..4096");
   if (w == out_w || h == out_h) return 0;  // one pass at most: no intermediate image
   return ((int64_t)h * out_w * 3 + 15) & ~(int64_t)15;
 }
@@ -259,16 +259,16 @@ extern "C" int64_t tpg_resize_workspace(int32_t h, int32_t w, int32_t out_h, int
 extern "C" int32_t tpg_resize_pack_job(void* jobs, int32_t index, const uint8_t* src, int32_t h, int32_t w,
                                        int32_t bands, int64_t row_stride, int32_t out_h, int32_t out_w,
                                        int64_t tab_h, int64_t tab_v, int64_t ws_off) {
-  if (!jobs || !src) return record_error(-10, "resize_pack_job: NULL pointer");
-  if (index < 0) return record_error(-2, "resize_pack_job: negative job index");
-  if (bands != 3) return record_error(-2, "resize_pack_job: images must have 3 interleaved bands (RGB)");
+  if (!jobs || !src) return fail(-10, "resize_pack_job: NULL pointer");
+  if (index < 0) return fail(-2, "resize_pack_job: negative job index");
+  if (bands != 3) return fail(-2, "resize_pack_job: images must have 3 interleaved bands (RGB)");
   if (!size_ok(h) || !size_ok(w) || !size_ok(out_h) || !size_ok(out_w))
-    return record_error(-2, "resize_pack_job: sizes must be in 1..4096");
-  if (row_stride < (int64_t)w * 3) return record_error(-2, "resize_pack_job: row stride smaller than W*3 bytes");
+    return fail(-2, "resize_pack_job: sizes must be in 1..4096");
+  if (row_stride < (int64_t)w * 3) return fail(-2, "resize_pack_job: row stride smaller than W*3 bytes");
   if ((w != out_w && tab_h < 0) || (h != out_h && tab_v < 0))
-    return record_error(-2, "resize_pack_job: negative table offset");
+    return fail(-2, "resize_pack_job: negative table offset");
   if (w != out_w && h != out_h && (ws_off < 0 || (ws_off & 15)))
-    return record_error(-2, "resize_pack_job: workspace offset must be a non-negative multiple of 16");
+    return fail(-2, "resize_pack_job: workspace offset must be a non-negative multiple of 16");
   ResizeJob j;
   j.src = src;
   j.row_stride = row_stride;
@@ -287,9 +287,10 @@ extern "C" int32_t tpg_resize_pack_job(void* jobs, int32_t index, const uint8_t*
 
 extern "C" int32_t tpg_resize_u8(int32_t njobs, const void* jobs_dev, const int32_t* tables_dev, int32_t out_h,
                                  int32_t out_w, uint8_t* out, void* ws, tpg_stream_t stream) {
+  if (int32_t grc = group_sync()) return grc;
   if (njobs == 0) return 0;
-  if (njobs < 0 || !size_ok(out_h) || !size_ok(out_w)) return record_error(-2, "resize_u8: bad sizes");
-  if (!jobs_dev || !tables_dev || !out) return record_error(-10, "resize_u8: NULL pointer");
+  if (njobs < 0 || !size_ok(out_h) || !size_ok(out_w)) return fail(-2, "resize_u8: bad sizes");
+  if (!jobs_dev || !tables_dev || !out) return fail(-10, "resize_u8: NULL pointer");
   // blocks of a job stride over its row chunks / output groups, so the grid needs no image size
   int per_job = 4096 / njobs;
   per_job = per_job < 1 ? 1 : (per_job > 512 ? 512 : per_job);
@@ -299,6 +300,5 @@ extern "C" int32_t tpg_resize_u8(int32_t njobs, const void* jobs_dev, const int3
                      out, static_cast<uint8_t*>(ws));
   hipLaunchKernelGGL(resize_v_kernel, grid, dim3(RS_THREADS), 0, (hipStream_t)stream, jobs, tables_dev, out_h, out_w,
                      out, static_cast<const uint8_t*>(ws));
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : record_error((int)e, hipGetErrorString(e));
+  return launched("resize_u8");
 }
