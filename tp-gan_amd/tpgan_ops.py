@@ -11,6 +11,7 @@ bfloat16 / float16 inside `with compute_dtype(torch.bfloat16)` (or torch.float16
 paths, fp32 accumulate.
 Master weights and their gradients stay float32.
 """
+import collections
 import contextlib
 import ctypes
 import os
@@ -366,54 +367,54 @@ def _time_launches(fn, reps=_TUNE_REPS):
 
 def _tuned_data_split(lib, d, op, device, launch):
     """(data_ksplit, data_algo) for this (op, shape): on first use the planner's own plan and
-    every (kernel, split) candidate are timed through launch(ws) with the descriptor set (a
-    workspace sized for it); a candidate replaces the planner's plan when it is faster by
-    DATA_TUNE["margin"] (0.97: 3 %).  That margin is within one trial's noise, so the plan and
-    the best candidate are timed a second time and each keeps its faster trial before the
-    comparison.  Returns the pick (also left in d.data_ksplit / d.data_algo)."""
-    d.data_ksplit, d.data_algo = 0, 0
+    every (kernel, split) candidate are timed through launch(desc, ws) on a scratch copy of d
+    with the candidate set (and a workspace sized for it); a candidate replaces the planner's
+    plan when it is faster by DATA_TUNE["margin"] (0.97: 3 %).  That margin is within one
+    trial's noise, so the plan and the best candidate are timed a second time and each keeps
+    its faster trial before the comparison.  Returns the pick for the caller to apply; d is
+    only read."""
     if not (AUTOTUNE["enabled"] and DATA_TUNE["enabled"]) or d.dtype == TPG_F32 or lib.tpg_get_deterministic():
         return (0, 0)
     key = ("dsplit", op, _desc_tuple(d) + (int(d.flags & FLAG_CONCURRENT), d.act))
     hit = AUTOTUNE["cache"].get(key)
     if hit is not None:
-        d.data_ksplit, d.data_algo = hit
         return hit
     if torch.cuda.is_current_stream_capturing() or AUTOTUNE["frozen"]:
         return (0, 0)
+    s = _launch_desc(d)
     times = {}
     torch.cuda.synchronize()
     for cand in [(0, 0)] + [(ks, al) for al in _DATA_ALGOS for ks in _DATA_SPLITS]:
-        d.data_ksplit, d.data_algo = cand
-        if cand[0] > 1 and lib.tpg_conv2d_workspace(ctypes.byref(d), op) > _DATA_SPLIT_WS_CAP:
+        s.data_ksplit, s.data_algo = cand
+        if cand[0] > 1 and lib.tpg_conv2d_workspace(ctypes.byref(s), op) > _DATA_SPLIT_WS_CAP:
             continue  # (a split this large never won; its partials would not fit L2 / MALL anyway)
-        ws = _ws(lib, d, op, device)
-        rc = launch(ws)
+        ws = _ws(lib, s, op, device)
+        rc = launch(s, ws)
         if rc:
             continue
-        times[cand] = _time_launches(lambda: check(launch(ws)))
+        times[cand] = _time_launches(lambda: check(launch(s, ws)))
         AUTOTUNE["trials"] += 1
     best = (0, 0)
     if times:
         kbest = min(times, key=times.get)
         if kbest != (0, 0) and (0, 0) in times:
             for cand in ((0, 0), kbest):  # (second trial of the two contenders)
-                d.data_ksplit, d.data_algo = cand
-                ws = _ws(lib, d, op, device)
-                times[cand] = min(times[cand], _time_launches(lambda: check(launch(ws))))
+                s.data_ksplit, s.data_algo = cand
+                ws = _ws(lib, s, op, device)
+                times[cand] = min(times[cand], _time_launches(lambda: check(launch(s, ws))))
         if (0, 0) not in times or times[kbest] < DATA_TUNE["margin"] * times[(0, 0)]:
             best = kbest
     torch.cuda.synchronize()
     AUTOTUNE["cache"][key] = best
     if DATA_TUNE["log"] is not None:
         DATA_TUNE["log"].append((op, _desc_tuple(d)[:8], times, best))
-    d.data_ksplit, d.data_algo = best
     return best
 
 
 def _tuned_wgrad(lib, d, x, g, dwv):
-    """(algo, ksplit) for this weight-gradient shape, tuning it on first use (pixel splits
-    capped at 16 for ops planned for a share of the chip)."""
+    """(algo, ksplit) for this weight-gradient shape, tuning it on first use on a scratch copy
+    of d and a scratch gradient (pixel splits capped at 16 for ops planned for a share of the
+    chip)."""
     key = _wgrad_key(d)
     hit = AUTOTUNE["cache"].get(key)
     if hit is not None:
@@ -424,14 +425,16 @@ def _tuned_wgrad(lib, d, x, g, dwv):
     npix = d.n * (d.in_h * d.in_w if d.transposed else d.out_h * d.out_w)
     nkt = (npix + 63) // 64
     best, best_ms = (0, 0), None
+    s = _launch_desc(d)
+
+    def launch():
+        return lib.tpg_conv2d_bwd_filter(ctypes.byref(s), tt(x), tt(g), tt(scratch), None, 0, stream_ptr())
     torch.cuda.synchronize()
     for algo in range(1, 14):
         for ks in _WG_SPLITS:
             if ks > nkt or (ks > 16 and (d.flags & FLAG_CONCURRENT)):
                 break
-            d.algo, d.ksplit = algo, ks
-            def launch():
-                return lib.tpg_conv2d_bwd_filter(ctypes.byref(d), tt(x), tt(g), tt(scratch), None, 0, stream_ptr())
+            s.algo, s.ksplit = algo, ks
             rc = launch()
             if rc == -30:  # algos 6..13 (row / image-halo kernel) do not cover this shape
                 break
@@ -440,7 +443,6 @@ def _tuned_wgrad(lib, d, x, g, dwv):
             AUTOTUNE["trials"] += 1
             if best_ms is None or t < best_ms:
                 best, best_ms = (algo, ks), t
-    d.algo, d.ksplit = 0, 0
     torch.cuda.synchronize()
     AUTOTUNE["cache"][key] = best
     return best
@@ -575,19 +577,29 @@ def _packed_tt(buf, dtype=TPG_BF16):
     return t
 
 
-def _run_maybe_packed(fn_packed, fn_plain, d, pk):
-    """Call with the packed image (desc flag set); fall back to packing inside the call
-    when the tensors need a different plan (-21)."""
+def _launch_desc(d, **fields):
+    """One launch's own descriptor: a copy of d with the named fields set.  A node's saved
+    descriptor (ctx.d) is written once, in its forward -- geometry, dtype, act, res_scale and
+    TPG_FLAG_CONCURRENT, every plan field zero -- and only read after that: whatever a launch
+    adds (the tuners' picks, WPACKED, DX_ACCUM, the effective act, in_act) goes into its copy."""
+    e = ConvDesc.from_buffer_copy(d)
+    for k, v in fields.items():
+        setattr(e, k, v)
+    return e
+
+
+def _run_maybe_packed(d, pk, wv, call, fallback=True):
+    """The status of call(desc, weight tensor) for launch descriptor d: with the packed image pk
+    (under a copy of d flagged WPACKED) when there is one, else with the fp32 weight wv, packed
+    inside the call.  A packed call refused because the tensors need a different plan (-21) is
+    re-run the second way and counted in PACK["fallbacks"]; with fallback=False (a tuner's
+    trial of one plan) the refusal is the answer."""
     if pk is not None:
-        base = d.flags
-        d.flags = base | FLAG_WPACKED
-        rc = fn_packed()
-        d.flags = base
-        if rc != -21:
-            check(rc)
-            return
+        rc = call(_launch_desc(d, flags=d.flags | FLAG_WPACKED), _packed_tt(pk))
+        if rc != -21 or not fallback:
+            return rc
         PACK["fallbacks"] += 1
-    check(fn_plain())
+    return call(d, tt(wv))
 
 
 _WS_BYTES = {}  # (op, descriptor) -> workspace bytes: the C planner runs once per shape, not per call
@@ -605,12 +617,18 @@ def _ws(lib, desc, op, device):
     return torch.empty(nb, dtype=torch.uint8, device=device)
 
 
-def _conv_act_forward(ctx, x, weight, bias, residual, geom, act, slope, res_scale, wparam, link_res=None, link_dx=None,
-                      keep=None, links=None):
+# What one conv2d call asks for besides its tensors (conv2d and conv2d_group build it with
+# _conv_call; the forward keeps it as ctx.call): the geometry, the fused activation, the residual
+# scale, the parameter the weight is (a view of), the GradLinks and the ActTokens (_act_links).
+_ConvCall = collections.namedtuple("_ConvCall", "geom act slope res_scale wparam link_res link_dx links")
+
+
+def _conv_act_forward(ctx, x, weight, bias, residual, call, keep=None):
     """_ConvAct's forward on any ctx with save_for_backward (a _MemberCtx inside a grouped
     node); keep: a list that holds every temporary a deferred (grouped) launch still reads."""
     lib = load()
     dtype = get_compute_dtype()
+    geom = call.geom
     ctx.in_dtype = x.dtype
     x = _fix_c1(to_cl(x, dtype))
     n, cin, h, w = x.shape
@@ -627,43 +645,33 @@ def _conv_act_forward(ctx, x, weight, bias, residual, geom, act, slope, res_scal
         res = _fix_c1(to_cl(residual, dtype))
         if tuple(res.shape) != (n, cout, oh, ow):
             raise RuntimeError("residual shape %s != output %s" % (tuple(res.shape), (n, cout, oh, ow)))
-    d = geom.desc(n, cin, h, w, cout, oh, ow, dtype, act, slope, res_scale)
+    d = geom.desc(n, cin, h, w, cout, oh, ow, dtype, call.act, call.slope, call.res_scale)
+    wparam = call.wparam if call.wparam is not None else weight
     wv = weight if weight.dtype == torch.float32 else weight.float()
-    pk = _packed_weight(wparam if wparam is not None else weight, d, OP_FWD, wv)
+    pk = _packed_weight(wparam, d, OP_FWD, wv)
     bptr = bias.data_ptr() if bias is not None else None
-    if keep is None:
-        def launch(ws_):
-            if pk is not None:
-                d.flags = d.flags | FLAG_WPACKED
-                try:
-                    return lib.tpg_conv2d_fwd(ctypes.byref(d), tt(x), _packed_tt(pk), bptr, tt(res), tt(_fix_c1(y)),
-                                              ws_.data_ptr(), ws_.numel(), stream_ptr())
-                finally:
-                    d.flags = d.flags & ~FLAG_WPACKED
-            return lib.tpg_conv2d_fwd(ctypes.byref(d), tt(x), tt(wv), bptr, tt(res), tt(_fix_c1(y)), ws_.data_ptr(),
-                                      ws_.numel(), stream_ptr())
-        _tuned_data_split(lib, d, OP_FWD, x.device, launch)
-    ws = _ws(lib, d, OP_FWD, x.device)
+
+    def fwd(e, wt, ws_):
+        return lib.tpg_conv2d_fwd(ctypes.byref(e), tt(x), wt, bptr, tt(res), tt(_fix_c1(y)), ws_.data_ptr(),
+                                  ws_.numel(), stream_ptr())
+    ld = d
+    if keep is None:  # (a grouped launch is deferred: there is nothing to time)
+        ld = _launch_desc(d)
+        ld.data_ksplit, ld.data_algo = _tuned_data_split(
+            lib, ld, OP_FWD, x.device,
+            lambda s, ws_: _run_maybe_packed(s, pk, wv, lambda e, wt: fwd(e, wt, ws_), fallback=False))
+    ws = _ws(lib, ld, OP_FWD, x.device)
     FLOPS["fwd"] += _conv_flops(d)
     e0 = _probe_begin(d, "fwd")
-    _run_maybe_packed(
-        lambda: lib.tpg_conv2d_fwd(ctypes.byref(d), tt(x), _packed_tt(pk), bptr, tt(res), tt(_fix_c1(y)),
-                                   ws.data_ptr(), ws.numel(), stream_ptr()),
-        lambda: lib.tpg_conv2d_fwd(ctypes.byref(d), tt(x), tt(wv), bptr, tt(res), tt(_fix_c1(y)),
-                                   ws.data_ptr(), ws.numel(), stream_ptr()), d, pk)
+    check(_run_maybe_packed(ld, pk, wv, lambda e, wt: fwd(e, wt, ws)))
     _probe_end(e0, d, "fwd")
     if keep is not None:
         keep += [ws, res, wv]
     ctx.save_for_backward(x, weight, y)
-    ctx.geom, ctx.act, ctx.slope, ctx.res_scale = geom, act, slope, res_scale
-    ctx.has_bias, ctx.has_res = bias is not None, residual is not None
-    ctx.d = d
-    ctx.wparam = wparam if wparam is not None else weight
-    ctx.bparam = bias
+    ctx.call, ctx.d = call, d
+    ctx.wparam, ctx.bparam = wparam, bias
     ctx.res_dtype = residual.dtype if residual is not None else None
-    ctx.x_dtype = x.dtype
-    ctx.link_res, ctx.link_dx = link_res, link_dx
-    ctx.act_in, ctx.act_out = links if links is not None else (None, None)
+    ctx.act_in, ctx.act_out = call.links if call.links is not None else (None, None)
     return y
 
 
@@ -673,91 +681,110 @@ class _ConvAct(torch.autograd.Function):
     saved input and output, never the pre-activation)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, residual, geom, act, slope, res_scale, wparam, link_res=None, link_dx=None,
-                links=None):
-        return _conv_act_forward(ctx, x, weight, bias, residual, geom, act, slope, res_scale, wparam, link_res,
-                                 link_dx, links=links)
+    def forward(ctx, x, weight, bias, residual, call):
+        return _conv_act_forward(ctx, x, weight, bias, residual, call)
 
     @staticmethod
     def backward(ctx, gy):
         if torch.is_grad_enabled():  # create_graph=True (WGAN-GP): differentiable backward
             _act_out_taken(ctx, gy, allowed=False)
-            return tuple(_conv_act_backward_graph(ctx, gy)) + (None, None, None)
-        if FUSED_BWD["enabled"]:
-            return _conv_act_backward_fused(ctx, gy) + (None, None, None)
-        _act_out_taken(ctx, gy, allowed=False)
-        return _ConvAct._backward_three_calls(ctx, gy) + (None, None, None)
+            grads = _conv_act_backward_graph(ctx, gy)
+        elif FUSED_BWD["enabled"]:
+            grads = _conv_act_backward_fused(ctx, gy)
+        else:
+            _act_out_taken(ctx, gy, allowed=False)
+            grads = _conv_act_backward_three_calls(ctx, gy)
+        return grads + (None,)  # (dx, dw, dbias, dres; the call record)
 
-    @staticmethod
-    def _backward_three_calls(ctx, gy):
-        lib = load()
-        x, weight, y = ctx.saved_tensors
-        d = ctx.d
-        d.data_ksplit, d.data_algo = 0, 0  # (the forward's pick)
-        dtype = y.dtype
-        n, cout, oh, ow = y.shape
-        g = new_act(n, cout, oh, ow, dtype, y.device)
-        dbias = None
-        fused_b = False
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            fused_b = _fused_target(ctx.bparam) is not None
-            dbias = ctx.bparam.grad if fused_b else torch.zeros(cout, dtype=torch.float32, device=y.device)
-        e0 = _probe_begin(d, "actb")
-        check(lib.tpg_act_bwd(n, cout, oh, ow, ctx.act, ctx.slope, tt(gy), tt(y), tt(_fix_c1(g)),
-                              dbias.data_ptr() if dbias is not None else None, stream_ptr()))
-        _probe_end(e0, d, "actb")
-        if fused_b:
-            dbias = None  # accumulated straight into bias.grad
-            _grad_ready(ctx.bparam)
-        g = _fix_c1(g)
-        dx = dw = dres = None
+
+# ---- what the backward paths share.  Each returns (dx, dw, dbias, dres).
+def _dw_target(ctx, weight):
+    """(the gradient to hand to autograd, the tensor the weight-gradient launch adds into):
+    (None, the flat gradient buffer's view) for a FlatParams-managed parameter, else twice a
+    fresh fp32 gradient laid out like the weight."""
+    tgt = _fused_target(ctx.wparam)
+    if tgt is not None:
+        return None, _grad_view(tgt, weight, ctx.wparam)
+    dw = torch.zeros(weight.shape, dtype=torch.float32, device=weight.device)
+    if weight.dim() == 4 and weight.is_contiguous(memory_format=torch.channels_last):
+        dw = dw.contiguous(memory_format=torch.channels_last)
+    return dw, dw
+
+
+def _dbias_target(ctx):
+    """(the buffer the bias gradient is added into or None, whether that is bias.grad itself)."""
+    if ctx.bparam is None or not ctx.needs_input_grad[2]:
+        return None, False
+    if _fused_target(ctx.bparam) is not None:
+        return ctx.bparam.grad, True
+    return torch.zeros(ctx.d.out_c, dtype=torch.float32, device=ctx.bparam.device), False
+
+
+def _res_grad(ctx, g):
+    """The residual's gradient res_scale * g (before any cast), None when it is not asked for."""
+    if ctx.res_dtype is None or not ctx.needs_input_grad[3]:
+        return None
+    return g if ctx.call.res_scale == 1.0 else g * ctx.call.res_scale
+
+
+def _cast_grad(t, dtype, what, grouped=False):
+    """t in the dtype autograd expects; a grouped backward refuses the cast (_deferred_read)."""
+    if t is not None and t.dtype != dtype:
+        if grouped:
+            _deferred_read(what)
+        t = t.to(dtype)
+    return t
+
+
+def _conv_act_backward_three_calls(ctx, gy):
+    lib = load()
+    x, weight, y = ctx.saved_tensors
+    d = ctx.d
+    dtype = y.dtype
+    n, cout, oh, ow = y.shape
+    g = new_act(n, cout, oh, ow, dtype, y.device)
+    dbias, fused_b = _dbias_target(ctx)
+    e0 = _probe_begin(d, "actb")
+    check(lib.tpg_act_bwd(n, cout, oh, ow, ctx.call.act, ctx.call.slope, tt(gy), tt(y), tt(_fix_c1(g)),
+                          dbias.data_ptr() if dbias is not None else None, stream_ptr()))
+    _probe_end(e0, d, "actb")
+    if fused_b:
+        dbias = None  # accumulated straight into bias.grad
+        _grad_ready(ctx.bparam)
+    g = _fix_c1(g)
+    dx = dw = None
+    if ctx.needs_input_grad[0]:
         wv = weight if weight.dtype == torch.float32 else weight.float()
-        if ctx.needs_input_grad[0]:
-            dx = new_act(*x.shape, dtype=dtype, device=x.device)
-            ws = _ws(lib, d, OP_BWD_DATA, x.device)
-            FLOPS["dgrad"] += _conv_flops(d)
-            e0 = _probe_begin(d, "dgrad")
-            pk = _packed_weight(ctx.wparam, d, OP_BWD_DATA, wv)
-            _run_maybe_packed(
-                lambda: lib.tpg_conv2d_bwd_data(ctypes.byref(d), tt(g), _packed_tt(pk), tt(_fix_c1(dx)), ws.data_ptr(),
-                                                ws.numel(), stream_ptr()),
-                lambda: lib.tpg_conv2d_bwd_data(ctypes.byref(d), tt(g), tt(wv), tt(_fix_c1(dx)), ws.data_ptr(),
-                                                ws.numel(), stream_ptr()), d, pk)
-            _probe_end(e0, d, "dgrad")
-            if dx.dtype != ctx.in_dtype:
-                dx = dx.to(ctx.in_dtype)
-        if ctx.needs_input_grad[1]:
-            tgt = _fused_target(ctx.wparam)
-            if tgt is not None:  # dW accumulates straight into the flat gradient buffer
-                dw = None
-                dwv = _grad_view(tgt, weight, ctx.wparam)
-            else:
-                dw = torch.zeros(weight.shape, dtype=torch.float32, device=weight.device)
-                if weight.dim() == 4 and weight.is_contiguous(memory_format=torch.channels_last):
-                    dw = dw.contiguous(memory_format=torch.channels_last)
-                dwv = dw
-            FLOPS["wgrad"] += _conv_flops(d)
-            algo, ks = _tuned_wgrad(lib, d, x, g, dwv)
-            d.algo, d.ksplit = algo, ks
-            e0 = _probe_begin(d, "wgrad")
-            check(lib.tpg_conv2d_bwd_filter(ctypes.byref(d), tt(x), tt(g), tt(dwv), None, 0, stream_ptr()))
-            _probe_end(e0, d, "wgrad")
-            d.algo, d.ksplit = 0, 0
-            if dw is None:
-                _grad_ready(ctx.wparam)
-            if dw is not None and dw.dtype != weight.dtype:
-                dw = dw.to(weight.dtype)
-        if ctx.has_res and ctx.needs_input_grad[3]:
-            dres = g if ctx.res_scale == 1.0 else g * ctx.res_scale
-            if dres.dtype != ctx.res_dtype:
-                dres = dres.to(ctx.res_dtype)
-        return dx, dw, dbias, dres, None, None, None, None, None
+        dx = new_act(*x.shape, dtype=dtype, device=x.device)
+        ws = _ws(lib, d, OP_BWD_DATA, x.device)
+        FLOPS["dgrad"] += _conv_flops(d)
+        e0 = _probe_begin(d, "dgrad")
+        pk = _packed_weight(ctx.wparam, d, OP_BWD_DATA, wv)
+        check(_run_maybe_packed(d, pk, wv, lambda e, wt: lib.tpg_conv2d_bwd_data(
+            ctypes.byref(e), tt(g), wt, tt(_fix_c1(dx)), ws.data_ptr(), ws.numel(), stream_ptr())))
+        _probe_end(e0, d, "dgrad")
+        dx = _cast_grad(dx, ctx.in_dtype, "an input-gradient dtype cast")
+    if ctx.needs_input_grad[1]:
+        dw, dwv = _dw_target(ctx, weight)
+        FLOPS["wgrad"] += _conv_flops(d)
+        algo, ks = _tuned_wgrad(lib, d, x, g, dwv)
+        e0 = _probe_begin(d, "wgrad")
+        check(lib.tpg_conv2d_bwd_filter(ctypes.byref(_launch_desc(d, algo=algo, ksplit=ks)), tt(x), tt(g), tt(dwv),
+                                        None, 0, stream_ptr()))
+        _probe_end(e0, d, "wgrad")
+        if dw is None:
+            _grad_ready(ctx.wparam)
+        dw = _cast_grad(dw, weight.dtype, "a weight-gradient dtype cast")
+    return dx, dw, dbias, _cast_grad(_res_grad(ctx, g), ctx.res_dtype, "a residual-gradient dtype cast")
 
 
 # Fused per-layer backward (tpg_conv2d_bwd): one C-ABI call per layer instead of
 # act_bwd + bwd_data + bwd_filter; for stride-1 "same" convs the activation' is applied in
 # the input-gradient kernel's halo staging and the bias gradient rides on the weight-gradient
 # kernel.  FUSED_BWD["enabled"] = False restores the three-call path (A/B, tests).
+# Either way a backward only READS the node's saved descriptor: it builds the launch's own
+# (_launch_desc: effective act, DX_ACCUM, then the tuners' picks and in_act) and drops it with
+# the call, so a launch that raises leaves nothing behind for a second backward of the graph.
 FUSED_BWD = {"enabled": True}
 
 
@@ -771,32 +798,26 @@ def _conv_act_backward_fused(ctx, gy, keep=None):
     grouped = keep is not None
     lib = load()
     x, weight, y = ctx.saved_tensors
-    d = ctx.d
+    call = ctx.call
     dtype = y.dtype
     n, cout, oh, ow = y.shape
     need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    need_db = ctx.has_bias and ctx.needs_input_grad[2]
     gy = _fix_c1(gy)
     # ActToken (producer side): the consumer's input-gradient launch already applied this conv's
     # act', so gy IS g -- the backward runs as that of the un-activated conv
-    act_eff = ACT_NONE if _act_out_taken(ctx, gy) else ctx.act
+    act_eff = ACT_NONE if _act_out_taken(ctx, gy) else call.act
     es = 4 if dtype == torch.float32 else 2
     g_is_gy = (act_eff == ACT_NONE and gy.dtype == dtype and gy.dim() == 4 and gy.stride(1) == 1 and
                gy.data_ptr() % 16 == 0 and all((gy.stride(i) * es) % 16 == 0 for i in (0, 2, 3)))
     g = gy if g_is_gy else _fix_c1(new_act(n, cout, oh, ow, dtype, y.device))
-    dbias = None
-    fused_b = False
-    if need_db:
-        fused_b = _fused_target(ctx.bparam) is not None
-        dbias = ctx.bparam.grad if fused_b else torch.zeros(cout, dtype=torch.float32, device=y.device)
+    dbias, fused_b = _dbias_target(ctx)
     # a residual block's parked shortcut gradient (GradLink): accumulated by the dgrad launch
     acc = None
-    if ctx.link_dx is not None and ctx.link_dx.g is not None:
-        acc, ctx.link_dx.g = ctx.link_dx.g, None
-    if need_dx and acc is not None and tuple(acc.shape) == tuple(x.shape) and acc.dtype == dtype:
-        dx = acc  # dgrad is added into the parked buffer in place
-        acc = None
-        d.flags = d.flags | FLAG_DX_ACCUM
+    if call.link_dx is not None and call.link_dx.g is not None:
+        acc, call.link_dx.g = call.link_dx.g, None
+    accum = bool(need_dx) and acc is not None and tuple(acc.shape) == tuple(x.shape) and acc.dtype == dtype
+    if accum:
+        dx, acc = acc, None  # dgrad is added into the parked buffer in place
     else:
         dx = new_act(*x.shape, dtype=dtype, device=x.device) if need_dx else None
     # ActToken (consumer side): x is the activated output of a conv whose only gradient is this
@@ -804,69 +825,46 @@ def _conv_act_backward_fused(ctx, gy, keep=None):
     # the launch leaves dx * act_x'(x) for that producer (desc.in_act)
     tok_in = ctx.act_in
     fuse_in = (tok_in is not None and ACT_LINK["enabled"] and need_dx and acc is None and
-               (ctx.link_dx is None or bool(d.flags & FLAG_DX_ACCUM)))
-    d.act = act_eff
-    if fuse_in:
-        d.in_act, d.in_slope = tok_in.act, tok_in.slope
-    try:
-        out = _conv_act_backward_fused_body(ctx, gy, keep, lib, x, weight, y, d, dtype, n, cout, oh, ow, need_dx, need_dw,
-                                            g_is_gy, g, dbias, fused_b, acc, dx, act_eff)
-    finally:
-        d.act = ctx.act
-        d.in_act, d.in_slope = ACT_NONE, 0.0
-    if fuse_in and out[0] is not None:
-        tok_in.take(out[0])
-    return out
-
-
-def _conv_act_backward_fused_body(ctx, gy, keep, lib, x, weight, y, d, dtype, n, cout, oh, ow, need_dx, need_dw,
-                                  g_is_gy, g, dbias, fused_b, acc, dx, act_eff):
-    grouped = keep is not None
-    dw = dwv = None
-    if need_dw:
-        tgt = _fused_target(ctx.wparam)
-        if tgt is not None:  # dW accumulates straight into the flat gradient buffer
-            dwv = _grad_view(tgt, weight, ctx.wparam)
-        else:
-            dw = torch.zeros(weight.shape, dtype=torch.float32, device=weight.device)
-            if weight.dim() == 4 and weight.is_contiguous(memory_format=torch.channels_last):
-                dw = dw.contiguous(memory_format=torch.channels_last)
-            dwv = dw
+               (call.link_dx is None or accum))
+    # the launch's descriptor, as the planner queries see it (packed image, k split, workspace)
+    ld = _launch_desc(ctx.d, act=act_eff, flags=ctx.d.flags | (FLAG_DX_ACCUM if accum else 0))
+    in_act, in_slope = (tok_in.act, tok_in.slope) if fuse_in else (ACT_NONE, 0.0)
+    dw, dwv = _dw_target(ctx, weight) if need_dw else (None, None)
     wv = weight if weight.dtype == torch.float32 else weight.float()
-    d.data_ksplit, d.data_algo = 0, 0  # (ctx.d carries the forward's pick)
-    pk = _packed_weight(ctx.wparam, d, OP_BWD_DATA, wv) if need_dx else None
+    pk = _packed_weight(ctx.wparam, ld, OP_BWD_DATA, wv) if need_dx else None
+
+    def bwd(e, wt, g_, dx_, dw_, db_, ws_):
+        wsp, wsn = (ws_.data_ptr(), ws_.numel()) if ws_ is not None else (None, 0)
+        return lib.tpg_conv2d_bwd(ctypes.byref(e), tt(x), wt, tt(y), tt(gy), tt(g_), tt(dx_), tt(dw_), db_, wsp, wsn,
+                                  stream_ptr())
     if need_dx and not grouped:
         # the input-gradient launch's k split, tuned on first use into scratch g / dx (the real
         # dx may hold a parked shortcut gradient it accumulates into)
         sc = []
 
-        def launch(ws_):
+        def trial(s, ws_):
             if not sc:
                 sc.extend([_fix_c1(new_act(n, cout, oh, ow, dtype, y.device)), _fix_c1(new_act(*x.shape, dtype=dtype,
                                                                                                device=x.device))])
-            if pk is not None:
-                d.flags = d.flags | FLAG_WPACKED
-            try:
-                return lib.tpg_conv2d_bwd(ctypes.byref(d), tt(x), _packed_tt(pk) if pk is not None else tt(wv), tt(y),
-                                          tt(gy), tt(gy if g_is_gy else sc[0]), tt(sc[1]), tt(None), None,
-                                          ws_.data_ptr(), ws_.numel(), stream_ptr())
-            finally:
-                d.flags = d.flags & ~FLAG_WPACKED
-        _tuned_data_split(lib, d, OP_BWD_DATA, x.device, launch)
+            return _run_maybe_packed(_launch_desc(s, in_act=in_act, in_slope=in_slope), pk, wv,
+                                     lambda e, wt: bwd(e, wt, gy if g_is_gy else sc[0], sc[1], None, None, ws_),
+                                     fallback=False)
+        ld.data_ksplit, ld.data_algo = _tuned_data_split(lib, ld, OP_BWD_DATA, x.device, trial)
         del sc
-    ws = _ws(lib, d, OP_BWD_DATA, x.device) if need_dx else None
-    wsp, wsn = (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
+    ws = _ws(lib, ld, OP_BWD_DATA, x.device) if need_dx else None
     # the weight-gradient tile / split is autotuned on a shape's first call, which needs g:
     # that call runs the fused op without dW, tunes on its g, then runs the weight gradient
-    key = _wgrad_key(d)
-    tune_first = (need_dw and AUTOTUNE["enabled"] and d.dtype != TPG_F32 and key not in AUTOTUNE["cache"] and
+    key = _wgrad_key(ld)
+    tune_first = (need_dw and AUTOTUNE["enabled"] and ld.dtype != TPG_F32 and key not in AUTOTUNE["cache"] and
                   not grouped)
+    # (what tpg_conv2d_bwd alone reads goes in after the planner queries)
+    ld.in_act, ld.in_slope = in_act, in_slope
     if need_dw and not tune_first:
-        d.algo, d.ksplit = AUTOTUNE["cache"].get(key, (0, 0))
+        ld.algo, ld.ksplit = AUTOTUNE["cache"].get(key, (0, 0))
     if need_dx:
-        FLOPS["dgrad"] += _conv_flops(d)
+        FLOPS["dgrad"] += _conv_flops(ld)
     if need_dw:
-        FLOPS["wgrad"] += _conv_flops(d)
+        FLOPS["wgrad"] += _conv_flops(ld)
     fx = _fix_c1(dx) if dx is not None else None
     dwt = dwv if (need_dw and not tune_first) else None
     bptr = dbias.data_ptr() if dbias is not None else None
@@ -876,28 +874,21 @@ def _conv_act_backward_fused_body(ctx, gy, keep, lib, x, weight, y, d, dtype, n,
     # (only where dW and the bias go into the flat buffers: a local dw buffer would otherwise be
     # dropped below.  A parked residual gradient is fine here: both calls stay on this stream,
     # ahead of the first conv's in-place write of it)
-    probe_w = (not grouped and dwt is not None and dw is None and (dbias is None or fused_b) and
-               not ctx.geom.transposed and PROBE["match"] is not None and PROBE["match"](d, "wgrad") and
-               not torch.cuda.is_current_stream_capturing())
-    split = probe_w
-    e0 = _probe_begin(d, "bwd")
-    _run_maybe_packed(
-        lambda: lib.tpg_conv2d_bwd(ctypes.byref(d), tt(x), _packed_tt(pk), tt(y), tt(gy), tt(g), tt(fx),
-                                   tt(None if split else dwt), None if split else bptr, wsp, wsn, stream_ptr()),
-        lambda: lib.tpg_conv2d_bwd(ctypes.byref(d), tt(x), tt(wv), tt(y), tt(gy), tt(g), tt(fx),
-                                   tt(None if split else dwt), None if split else bptr, wsp, wsn, stream_ptr()), d, pk)
-    _probe_end(e0, d, "bwd", _conv_flops(d) * (int(bool(need_dx)) + int(bool(need_dw and not tune_first and not split))))
-    d.flags = d.flags & ~FLAG_DX_ACCUM
+    split = (not grouped and dwt is not None and dw is None and (dbias is None or fused_b) and
+             not ld.transposed and PROBE["match"] is not None and PROBE["match"](ld, "wgrad") and
+             not torch.cuda.is_current_stream_capturing())
+    e0 = _probe_begin(ld, "bwd")
+    check(_run_maybe_packed(ld, pk, wv, lambda e, wt: bwd(e, wt, g, fx, None if split else dwt,
+                                                         None if split else bptr, ws)))
+    _probe_end(e0, ld, "bwd", _conv_flops(ld) * (int(bool(need_dx)) + int(bool(need_dw and not tune_first and not split))))
     if grouped:
         keep += [ws, g, gy, wv]
     if split:
         gt = gy if g_is_gy else g  # (g now holds act'(y) * gy: the second call takes it as is)
-        d2 = _plain_desc(d)
-        d2.algo, d2.ksplit = d.algo, d.ksplit
-        ew = _probe_begin(d, "wgrad")
-        check(lib.tpg_conv2d_bwd(ctypes.byref(d2), tt(x), tt(None), tt(None), tt(gt), tt(gt), tt(None), tt(dwt),
-                                 bptr, None, 0, stream_ptr()))
-        _probe_end(ew, d, "wgrad")
+        ew = _probe_begin(ld, "wgrad")
+        check(lib.tpg_conv2d_bwd(ctypes.byref(_plain_desc(ctx.d, algo=ld.algo, ksplit=ld.ksplit)), tt(x), tt(None),
+                                 tt(None), tt(gt), tt(gt), tt(None), tt(dwt), bptr, None, 0, stream_ptr()))
+        _probe_end(ew, ld, "wgrad")
         if fused_b:
             _grad_ready(ctx.bparam)
         _grad_ready(ctx.wparam)
@@ -910,41 +901,33 @@ def _conv_act_backward_fused_body(ctx, gy, keep, lib, x, weight, y, d, dtype, n,
             _deferred_read("the parked shortcut gradient's add")
         dx = dx + acc
     if tune_first:
-        algo, ks = _tuned_wgrad(lib, d, x, g, dwv)
-        d.algo, d.ksplit = algo, ks
-        check(lib.tpg_conv2d_bwd_filter(ctypes.byref(d), tt(x), tt(g), tt(dwv), None, 0, stream_ptr()))
-    d.algo, d.ksplit = 0, 0
+        wd = _launch_desc(ctx.d, act=act_eff)
+        wd.algo, wd.ksplit = _tuned_wgrad(lib, wd, x, g, dwv)
+        check(lib.tpg_conv2d_bwd_filter(ctypes.byref(wd), tt(x), tt(g), tt(dwv), None, 0, stream_ptr()))
     if fused_b:
         dbias = None  # accumulated straight into bias.grad
         _grad_ready(ctx.bparam)
     if need_dw:
         if dw is None:
             _grad_ready(ctx.wparam)
-        elif dw.dtype != weight.dtype:
-            if grouped:
-                _deferred_read("a weight-gradient dtype cast")
-            dw = dw.to(weight.dtype)
-    if dx is not None and dx.dtype != ctx.in_dtype:
-        if grouped:
-            _deferred_read("an input-gradient dtype cast")
-        dx = dx.to(ctx.in_dtype)
-    dres = None
-    if ctx.has_res and ctx.needs_input_grad[3]:
-        dres = g if ctx.res_scale == 1.0 else g * ctx.res_scale
+        dw = _cast_grad(dw, weight.dtype, "a weight-gradient dtype cast", grouped)
+    dx = _cast_grad(dx, ctx.in_dtype, "an input-gradient dtype cast", grouped)
+    dres = _res_grad(ctx, g)
+    if dres is not None:
         # (gy itself only when it is the ActToken consumer's input gradient: then this backward
         # owns it, and the first conv may accumulate into it in place)
-        if ctx.link_res is not None and (dres is not gy or act_eff == ACT_NONE and ctx.act != ACT_NONE) and \
+        if call.link_res is not None and (dres is not gy or act_eff == ACT_NONE and call.act != ACT_NONE) and \
                 dres.dtype == dtype:
             # park it for the block's first conv (its input-gradient launch adds it)
-            ctx.link_res.g = dres
+            call.link_res.g = dres
             dres = None
-        elif dres.dtype != ctx.res_dtype:
-            if grouped:
-                _deferred_read("a residual-gradient dtype cast")
-            dres = dres.to(ctx.res_dtype)
+        else:
+            dres = _cast_grad(dres, ctx.res_dtype, "a residual-gradient dtype cast", grouped)
     if grouped and dres is not None and dres is not g and dres is not gy:
         _deferred_read("the scaled residual gradient")
-    return dx, dw, dbias, dres, None, None, None, None, None
+    if fuse_in and dx is not None:
+        tok_in.take(dx)
+    return dx, dw, dbias, dres
 
 
 # ---- double backward (WGAN-GP): the backward of _ConvAct written as
@@ -955,12 +938,10 @@ def _conv_act_backward_fused_body(ctx, gy, keep, lib, x, weight, y, d, dtype, n,
 #   dx = dgrad(g, w)      d/dg: fwd(., w)      d/dw: wgrad(., g)
 #   dw = wgrad(x, g)      d/dx: dgrad(g, .)    d/dg: fwd(x, .)
 #   y' = fwd(x, w)        d/dx: dgrad(., w)    d/dw: wgrad(x, .)
-def _plain_desc(d):
-    e = ConvDesc()
-    ctypes.memmove(ctypes.byref(e), ctypes.byref(d), ctypes.sizeof(ConvDesc))
-    e.act, e.slope, e.res_scale, e.ksplit, e.algo, e.data_ksplit, e.data_algo = ACT_NONE, 0.0, 1.0, 0, 0, 0, 0
-    e.in_act, e.in_slope = ACT_NONE, 0.0
-    return e
+def _plain_desc(d, **fields):
+    """The bare conv of a node's saved descriptor d (no activation, no residual), shared read-only
+    by the Functions below."""
+    return _launch_desc(d, act=ACT_NONE, slope=0.0, res_scale=1.0, **fields)
 
 
 class _ActMask(torch.autograd.Function):
@@ -994,11 +975,8 @@ class _ConvFwdPlain(torch.autograd.Function):
         FLOPS["fwd"] += _conv_flops(d)
         wv = w.float()
         pk = _packed_weight(wp, d, OP_FWD, wv) if wp is not None else None
-        _run_maybe_packed(
-            lambda: lib.tpg_conv2d_fwd(ctypes.byref(d), tt(x), _packed_tt(pk), None, TpgTensor(), tt(_fix_c1(y)),
-                                       ws.data_ptr(), ws.numel(), stream_ptr()),
-            lambda: lib.tpg_conv2d_fwd(ctypes.byref(d), tt(x), tt(wv), None, TpgTensor(), tt(_fix_c1(y)),
-                                       ws.data_ptr(), ws.numel(), stream_ptr()), d, pk)
+        check(_run_maybe_packed(d, pk, wv, lambda e, wt: lib.tpg_conv2d_fwd(
+            ctypes.byref(e), tt(x), wt, None, TpgTensor(), tt(_fix_c1(y)), ws.data_ptr(), ws.numel(), stream_ptr())))
         ctx.save_for_backward(x, w)
         ctx.d = d
         ctx.wp = wp
@@ -1022,11 +1000,8 @@ class _ConvDgrad(torch.autograd.Function):
         FLOPS["dgrad"] += _conv_flops(d)
         wv = w.float()
         pk = _packed_weight(wp, d, OP_BWD_DATA, wv) if wp is not None else None
-        _run_maybe_packed(
-            lambda: lib.tpg_conv2d_bwd_data(ctypes.byref(d), tt(g), _packed_tt(pk), tt(_fix_c1(dx)), ws.data_ptr(),
-                                            ws.numel(), stream_ptr()),
-            lambda: lib.tpg_conv2d_bwd_data(ctypes.byref(d), tt(g), tt(wv), tt(_fix_c1(dx)), ws.data_ptr(),
-                                            ws.numel(), stream_ptr()), d, pk)
+        check(_run_maybe_packed(d, pk, wv, lambda e, wt: lib.tpg_conv2d_bwd_data(
+            ctypes.byref(e), tt(g), wt, tt(_fix_c1(dx)), ws.data_ptr(), ws.numel(), stream_ptr())))
         ctx.save_for_backward(g, w)
         ctx.d = d
         ctx.wp = wp
@@ -1076,22 +1051,16 @@ def _conv_act_backward_graph(ctx, gy):
         weight = wp.as_strided(weight.shape, weight.stride(), weight.storage_offset())
     d = _plain_desc(ctx.d)
     g = _ActMask.apply(gy, y, ctx.d.act, ctx.d.slope)
-    dx = dw = dbias = dres = None
+    dx = dw = dbias = None
     if ctx.needs_input_grad[0]:
-        dx = _ConvDgrad.apply(g, weight, d, wp)
-        if dx.dtype != ctx.in_dtype:
-            dx = dx.to(ctx.in_dtype)
+        dx = _cast_grad(_ConvDgrad.apply(g, weight, d, wp), ctx.in_dtype, "an input-gradient dtype cast")
     if ctx.needs_input_grad[1]:
         dw = _ConvWgrad.apply(x, g, d)
         if tuple(dw.shape) != tuple(weight.shape):
             dw = dw.reshape(weight.shape)
-    if ctx.has_bias and ctx.needs_input_grad[2]:
+    if ctx.bparam is not None and ctx.needs_input_grad[2]:
         dbias = g.float().sum((0, 2, 3))
-    if ctx.has_res and ctx.needs_input_grad[3]:
-        dres = g if ctx.res_scale == 1.0 else g * ctx.res_scale
-        if dres.dtype != ctx.res_dtype:
-            dres = dres.to(ctx.res_dtype)
-    return dx, dw, dbias, dres, None, None, None, None, None
+    return dx, dw, dbias, _cast_grad(_res_grad(ctx, g), ctx.res_dtype, "a residual-gradient dtype cast")
 
 
 # Data-parallel overlap (tpgan_train.OverlappedGradSync): called once the last kernel that
@@ -1141,16 +1110,22 @@ def conv2d(x, weight, bias=None, stride=(1, 1), pad=(0, 0, 0, 0), pad_mode=PAD_Z
     and its first conv (input = the block input), see GradLink.  act_in_ok: the caller's
     promise that x is consumed by this conv alone (with link_dx: and by the shortcut whose
     gradient the link carries into this conv's input gradient) -- see ActToken."""
+    call = _conv_call(x, weight, stride, pad, pad_mode, act, res_scale, transposed, output_padding, wparam, link_res,
+                      link_dx, act_in_ok)
+    y = _ConvAct.apply(x, weight, bias, residual, call)
+    _set_act_token(call.links, y)
+    return y
+
+
+def _conv_call(x, weight, stride=(1, 1), pad=(0, 0, 0, 0), pad_mode=PAD_ZERO, act=None, res_scale=1.0,
+               transposed=False, output_padding=(0, 0), wparam=None, link_res=None, link_dx=None, act_in_ok=False):
+    """The _ConvCall of conv2d's keyword arguments (the tensors bias / residual aside)."""
     code = act_code(act)
     if code is None:
         raise ValueError("activation %r cannot be fused" % (act,))
-    kh, kw = weight.shape[2], weight.shape[3]
-    geom = ConvGeom(kh, kw, stride, pad, pad_mode, transposed, output_padding)
-    links = _act_links(x, code, act_in_ok)
-    y = _ConvAct.apply(x, weight, bias, residual, geom, code[0], code[1], float(res_scale), wparam, link_res,
-                       link_dx, links)
-    _set_act_token(links, y)
-    return y
+    geom = ConvGeom(weight.shape[2], weight.shape[3], stride, pad, pad_mode, transposed, output_padding)
+    return _ConvCall(geom, code[0], code[1], float(res_scale), wparam, link_res, link_dx,
+                     _act_links(x, code, act_in_ok))
 
 
 def _act_links(x, code, act_in_ok):
@@ -1258,16 +1233,16 @@ class _ConvActGroup(torch.autograd.Function):
     """n _ConvAct calls on independent inputs as one autograd node (see GROUP)."""
 
     @staticmethod
-    def forward(ctx, specs, *flat):
+    def forward(ctx, calls, *flat):
         lib = load()
         keep, subs, outs = [], [], []
         lib.tpg_group_begin()
         try:
-            for m, sp in enumerate(specs):
+            for m, call in enumerate(calls):
                 x, w, b, r = flat[4 * m:4 * m + 4]
                 lib.tpg_group_member()
                 sc = _MemberCtx()
-                outs.append(_conv_act_forward(sc, x, w, b, r, *sp[:7], keep=keep, links=sp[7]))
+                outs.append(_conv_act_forward(sc, x, w, b, r, call, keep=keep))
                 subs.append(sc)
         finally:
             rc = lib.tpg_group_end()
@@ -1285,12 +1260,12 @@ class _ConvActGroup(torch.autograd.Function):
         saved = ctx.saved_tensors
         for m, sc in enumerate(ctx.subs):
             sc.saved_tensors = saved[3 * m:3 * m + 3]
-            sc.needs_input_grad = tuple(ctx.needs_input_grad[1 + 4 * m:5 + 4 * m]) + (False,) * 5
+            sc.needs_input_grad = tuple(ctx.needs_input_grad[1 + 4 * m:5 + 4 * m])
         grads = []
         if torch.is_grad_enabled():  # create_graph (WGAN-GP): members one by one, differentiable
             for sc, gy in zip(ctx.subs, gys):
                 _act_out_taken(sc, gy, allowed=False)  # (as _ConvAct.backward: no linked act' here)
-                grads += list(_conv_act_backward_graph(sc, gy)[:4])
+                grads += _conv_act_backward_graph(sc, gy)
         elif FUSED_BWD["enabled"]:
             lib = load()
             keep, ready = [], []
@@ -1299,7 +1274,7 @@ class _ConvActGroup(torch.autograd.Function):
             try:
                 for sc, gy in zip(ctx.subs, gys):
                     lib.tpg_group_member()
-                    grads += list(_conv_act_backward_fused(sc, gy, keep=keep)[:4])
+                    grads += _conv_act_backward_fused(sc, gy, keep=keep)
             finally:
                 _READY_DEFER.pop()
                 rc = lib.tpg_group_end()
@@ -1309,7 +1284,7 @@ class _ConvActGroup(torch.autograd.Function):
         else:
             for sc, gy in zip(ctx.subs, gys):
                 _act_out_taken(sc, gy, allowed=False)
-                grads += list(_ConvAct._backward_three_calls(sc, gy)[:4])
+                grads += _conv_act_backward_three_calls(sc, gy)
         for sc in ctx.subs:
             sc.saved_tensors = None
         return (None,) + tuple(grads)
@@ -1322,18 +1297,11 @@ def conv2d_group(calls):
         return [conv2d(**c) for c in calls]
     specs, flat = [], []
     for c in calls:
-        code = act_code(c.get("act"))
-        if code is None:
-            raise ValueError("activation %r cannot be fused" % (c.get("act"),))
-        weight = c["weight"]
-        geom = ConvGeom(weight.shape[2], weight.shape[3], c.get("stride", (1, 1)), c.get("pad", (0, 0, 0, 0)),
-                        c.get("pad_mode", PAD_ZERO), c.get("transposed", False), c.get("output_padding", (0, 0)))
-        specs.append((geom, code[0], code[1], float(c.get("res_scale", 1.0)), c.get("wparam"), c.get("link_res"),
-                      c.get("link_dx"), _act_links(c["x"], code, c.get("act_in_ok", False))))
-        flat += [c["x"], weight, c.get("bias"), c.get("residual")]
+        specs.append(_conv_call(**{k: v for k, v in c.items() if k not in ("bias", "residual")}))
+        flat += [c["x"], c["weight"], c.get("bias"), c.get("residual")]
     outs = list(_ConvActGroup.apply(specs, *flat))
-    for sp, y in zip(specs, outs):
-        _set_act_token(sp[7], y)
+    for call, y in zip(specs, outs):
+        _set_act_token(call.links, y)
     return outs
 
 
