@@ -387,6 +387,42 @@ int32_t tpg_ssd_loss_bwd(int32_t B, int32_t n, int32_t C, const float* pred, con
 int32_t tpg_ssd_decode(int32_t B, int32_t n, int32_t C, const float* loc, const float* cls, float conf, float nms_thr,
                        int32_t top_k, int32_t* keep, float* score, tpg_stream_t stream);
 
+/* Landmark front end: the detector's head outputs -> the four crop centres and crop boxes of
+ * process() (DataAndDataset.py:42-54), with nothing leaving the device, and Pretrain.py's accuracy
+ * measure (:17-64) for a batch.  loc / cls as above; every other pointer dense device memory unless
+ * marked HOST.
+ *   tpg_ssd_landmarks      per image and landmark class l in 0..3 (left eye, right eye, nose, mouth
+ *                          centre) the best anchor: the largest score expf(x[l] - logsumexp(x)) --
+ *                          tpg_ssd_decode's own expression, bit for bit -- the smallest index among
+ *                          equal scores, a NaN score never.  This is slot 0 of tpg_ssd_decode with
+ *                          top_k = 1 wherever that slot is not -1.  1 <= n <= TPG_SSD_MAXN.
+ *                            scale    device float[B][2] (sx, sy) multiplied into the point in float32
+ *                                     (as tpg_landmark_boxes), or NULL
+ *                            patch_wh HOST int32[4][2], as tpg_landmark_boxes
+ *                            points   (B, 4, 2) loc[b][anchor] (* scale); NaN when no score was a number
+ *                            score    (B, 4) the best score (0 when none), anchor (B, 4) its index (-1)
+ *                            boxes    (B, 4, 4) left, upper, right, lower: with x, y the floorf of the
+ *                                     point, x - pw/2 + 1, y - ph/2 + 1, x + pw/2 + 1, y + ph/2 + 1
+ *                            status   (B): bit l (1, 2, 4, 8) set when landmark l was not found
+ *                                     (found: score > conf, strictly, as the decoder; the best
+ *                                     anchor's point and box are written all the same); bit 4 (16) set
+ *                                     when a chosen coordinate is NaN, infinite or |v| > 1e9 (that
+ *                                     coordinate counts as 0 in the box, as tpg_landmark_boxes)
+ *                          Every output slot is written on every call.
+ *   tpg_landmark_accuracy  acc (B) = mean over the four landmarks of weights[i] where
+ *                          thresholds[i-1] < d <= thresholds[i] (thresholds[-1] = 0), else 0, with
+ *                          d = sqrtf(dx*dx + dy*dy) in float32 without FMA contraction between pred
+ *                          and truth (both (B, 4, 2)).  As the reference, d == 0 scores 0; so do a NaN
+ *                          d and a landmark whose bit is set in status (tpg_ssd_landmarks's; may be
+ *                          NULL).  thresholds / weights: HOST float[nbands], thresholds ascending,
+ *                          1 <= nbands <= TPG_LM_MAX_BANDS. */
+#define TPG_LM_MAX_BANDS 8
+int32_t tpg_ssd_landmarks(int32_t B, int32_t n, int32_t C, const float* loc, const float* cls, float conf,
+                          const float* scale, const int32_t* patch_wh, float* points, float* score, int32_t* anchor,
+                          int32_t* boxes, int32_t* status, tpg_stream_t stream);
+int32_t tpg_landmark_accuracy(int32_t B, const float* pred, const float* truth, const int32_t* status, int32_t nbands,
+                              const float* thresholds, const float* weights, float* acc, tpg_stream_t stream);
+
 /* Depthwise Conv2d (groups == in_c == out_c, MobileNetV2.py:105), kernels up to 3x3, zero
  * padding: y = act(dwconv(x, w) + bias [+ res_scale * residual]).  w logical [C][1][kh][kw]
  * fp32 (any strides); x / y / residual channels-last, 16-byte aligned rows of desc.dtype. */
@@ -461,6 +497,13 @@ int32_t tpg_landmark_boxes(int32_t n, int32_t npts, const float* lm, const float
 int32_t tpg_crop_normalize(int32_t n, int32_t c, int32_t in_h, int32_t in_w, const uint8_t* img,
                            const int64_t* img_stride, int32_t njobs, const tpg_tensor* outs, const int32_t* out_hw,
                            const int32_t* slots, const int32_t* boxes, int32_t box_stride, tpg_stream_t stream);
+/* torchvision's ToTensor() on the device (Pretrain.py trains the landmark detector on it):
+ * out[b, c, y, x] = (float)img[b, c, y, x] / 255.0f, an IEEE division, no FMA contraction, stored as
+ * TPG_F32 / TPG_BF16 / TPG_F16 into a logical-NCHW tensor of any strides (channels-last in the
+ * detector's compute dtype: its first conv then takes it as it is).  img_stride: HOST int64[4]
+ * element strides of the u8 image's logical (n, c, h, w) view, as tpg_crop_normalize; n*h*w < 2^31. */
+int32_t tpg_u8_to_unit(int32_t n, int32_t c, int32_t h, int32_t w, const uint8_t* img, const int64_t* img_stride,
+                       tpg_tensor out, tpg_stream_t stream);
 
 /* Pillow's 8-bit LANCZOS resize of RGB (HWC, 3 interleaved bands) images, byte for byte what
  * Image.resize((out_w, out_h), Image.LANCZOS) returns (DataAndDataset.py:247-251), for a batch of

@@ -27,6 +27,15 @@ Frontalizer in bf16 on a resident batch of synthetic raw WxH photos with synthet
     similarity matrix the fused search never writes;
   - IdentityScorer.embed at B = 32 with the ResNet-18 back-end in bf16.
 
+--detect runs the landmark-detector leg instead (profiles/r11/landmarks.txt), in one process, bf16,
+B = 32 synthetic raw photos, after warm-up, HIP events and the host clock around each:
+
+  - LandmarkDetector.detect (resize, u8_to_unit, MobileNetV2 + SSD head, ssd_landmarks, status read);
+  - Frontalizer(imgs) with the detector attached and no landmarks given;
+  - the decode-to-boxes step alone, tpgan_ops.ssd_landmarks as back-to-back launches, and as its
+    baseline the route there was before it on the same tensors: MultiTaskDecoder()(loc, cls), the
+    lists assembled into a host array, uploaded, FaceBatcher.landmark_boxes.
+
 Prints one JSON line per measurement; --out also writes them to a file.
 """
 import argparse
@@ -112,6 +121,85 @@ def identity_leg(a, emit):
           "faces_per_s": round(B / (ms * 1e-3), 1)})
 
 
+def detect_leg(a, emit):
+    import D_and_G_model as DG
+    import MobileNetV2 as MN
+    import tpgan_infer
+    import tpgan_ops
+    from DataAndDataset import FaceBatcher
+    dev = torch.device("cuda", 0)
+    w, h = (int(v) for v in a.raw.lower().split("x"))
+    B = a.batch
+    rng = np.random.default_rng(0)
+    imgs = [torch.from_numpy(rng.integers(0, 256, (h, w, 3), dtype=np.uint8)).to(dev) for _ in range(B)]
+    torch.manual_seed(0)
+    # untrained weights: no score reaches a confidence threshold, so every landmark takes its best
+    # anchor (on_missing="best"); the work per call is that of a trained detector
+    det = tpgan_infer.LandmarkDetector(MN.MobileNetV2(), device=dev, compute_dtype=torch.bfloat16, max_batch=B,
+                                       on_missing="best")
+    fz = tpgan_infer.Frontalizer(DG.Generator(64, 347, use_batchnorm=False), device=dev, compute_dtype=torch.bfloat16,
+                                 max_batch=B, detector=det)
+    for _ in range(3):
+        d = det.detect(imgs)
+        fz(imgs)
+    torch.cuda.synchronize()
+    iters, kiters = max(a.iters, 100), max(a.kiters, 2000)  # windows of a few hundred ms and of ~30 ms
+
+    def rounds(fn, n):
+        t = [events(fn, n) for _ in range(a.rounds)]
+        ev, wl = [x[0] for x in t], [x[1] for x in t]
+        return float(np.median(ev)), float(np.median(wl)), [round(min(ev), 4), round(max(ev), 4)]
+    ms, wall, mm = rounds(lambda: det.detect(imgs), iters)
+    emit({"op": "LandmarkDetector.detect (raw %dx%d photos -> points, boxes, status), bf16" % (w, h), "batch": B,
+          "rounds": a.rounds, "calls_per_round": iters, "ms_per_batch": round(ms, 3), "ms_per_batch_min_max": mm,
+          "ms_per_batch_host_clock": round(wall, 3), "faces_per_s": round(B / (ms * 1e-3), 1),
+          "note": "ends with the one status read of the batch"})
+    ms, wall, mm = rounds(lambda: fz(imgs), iters)
+    emit({"op": "Frontalizer.__call__ with the detector, no landmarks given (raw %dx%d -> u8 128x128x3), bf16" % (w, h),
+          "batch": B, "rounds": a.rounds, "calls_per_round": iters, "ms_per_batch": round(ms, 3),
+          "ms_per_batch_min_max": mm, "ms_per_batch_host_clock": round(wall, 3),
+          "faces_per_s": round(B / (ms * 1e-3), 1)})
+
+    # the decode-to-boxes step alone, on the head outputs of the same photos
+    with torch.no_grad():
+        loc, cls = det._head(d["u8_128"])
+    n = loc.shape[1]
+    conf = 0.0  # both routes then decode a point for every class of every face
+    for _ in range(5):
+        fused = tpgan_ops.ssd_landmarks(loc, cls, conf)
+    torch.cuda.synchronize()
+
+    dec = MN.MultiTaskDecoder(confidence_threshold=conf, top_k=1)
+    fb4 = FaceBatcher(dev, pts_idx=[[0, 0], [1, 1], [2, 2], [3, 3], [3, 3]], check=False)
+
+    def today():
+        out = dec(loc, cls)  # tpg_ssd_decode, keep / score to the host, lists of tuples per image
+        pts = torch.stack([torch.stack([p for c, _, p in res if c < 4]) for res in out])
+        host = pts.cpu().numpy().astype(np.float32)  # the landmark array reassembled on the host ...
+        return fb4.landmark_boxes(torch.from_numpy(host).to(dev))  # ... uploaded again, then the box kernel
+    for _ in range(3):
+        base = today()
+    torch.cuda.synchronize()
+    same = bool(torch.equal(base[1], fused[3]))
+    t_f, t_b = [], []
+    for _ in range(a.rounds):  # interleaved: the two routes alternate on the same box
+        t_f.append(events(lambda: tpgan_ops.ssd_landmarks(loc, cls, conf), kiters))
+        t_b.append(events(today, iters))
+    ms, wall = (float(np.median([x[i] for x in t_f])) for i in (0, 1))
+    bms, bwall = (float(np.median([x[i] for x in t_b])) for i in (0, 1))
+    line = {"op": "decode to crop boxes: tpg_ssd_landmarks, back-to-back launches", "batch": B, "anchors": n,
+            "rounds": a.rounds, "calls_per_round": kiters, "us_per_call": round(ms * 1e3, 2),
+            "us_per_call_min_max": [round(min(x[0] for x in t_f) * 1e3, 2), round(max(x[0] for x in t_f) * 1e3, 2)],
+            "us_per_call_host_clock": round(wall * 1e3, 2), "device_to_host_copies": 0}
+    line.update({"baseline_calls_per_round": iters,
+                 "baseline_us_per_call_min_max": [round(min(x[0] for x in t_b) * 1e3, 2),
+                                                  round(max(x[0] for x in t_b) * 1e3, 2)],
+                 "baseline": "MultiTaskDecoder()(loc, cls) -> lists -> host array -> upload -> FaceBatcher.landmark_boxes",
+                 "baseline_us_per_call": round(bms * 1e3, 2), "baseline_us_per_call_host_clock": round(bwall * 1e3, 2),
+                 "baseline_over_fused_host_clock": round(bwall / wall, 2), "boxes_equal": same})
+    emit(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -121,17 +209,18 @@ def main():
     ap.add_argument("--big", type=int, default=1024, help="faces of the kernels-alone line")
     ap.add_argument("--identity", action="store_true", help="the identity-scoring leg instead of the image path")
     ap.add_argument("--rounds", type=int, default=5, help="interleaved rounds of the identity leg")
+    ap.add_argument("--detect", action="store_true", help="the landmark-detector leg instead of the image path")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_infer.py needs a ROCm GPU (there is no CPU path)")
-    if a.identity:
+    if a.identity or a.detect:
         lines = []
 
         def emit_id(d):
             lines.append(json.dumps(d))
             print(lines[-1], flush=True)
-        identity_leg(a, emit_id)
+        (identity_leg if a.identity else detect_leg)(a, emit_id)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:

@@ -24,6 +24,9 @@
 // of (P, G, k, gchunk) up to 2^24 rows, whose size must be positive, hold at least one k-entry list
 // per probe and chunk and not shrink when P or the number of chunks grows, and every argument the
 // three launch entry points reject (which must stop them before any device work).
+// The landmark front end's entry points (tpg_ssd_landmarks, tpg_landmark_accuracy, tpg_u8_to_unit)
+// likewise: NULL pointers and sizes outside their ranges (n = 0 and 4097, C = 4, 0 and 9 bands, ...),
+// with the host-read tables (patch sizes, band edges and weights, strides) in exact-size heap blocks.
 // Built with `make -C tp-gan_amd asan` (the host-logic units compiled with -fsanitize=address on
 // the host side only; the kernels are the product's) and run by tests/test_capi.py.
 // Exit status: 0 clean, 1 a consistency check failed; ASan aborts on a memory error.
@@ -411,6 +414,86 @@ static void identity_sweep(long iters) {
   if (accepted) { fprintf(stderr, "identity: %d malformed calls accepted\n", accepted); g_fail = 1; }
 }
 
+// Landmark front end: tpg_ssd_landmarks, tpg_landmark_accuracy and tpg_u8_to_unit must refuse every
+// malformed call below before any device work, -2 for sizes and -10 for NULL pointers.  The device
+// pointers are never dereferenced on the host; the HOST arrays are heap blocks of exactly their size.
+static void landmark_sweep() {
+  int wrong = 0;
+  float* f = (float*)0x10000;
+  int32_t* i32 = (int32_t*)0x20000;
+  uint8_t* u8 = (uint8_t*)0x30000;
+  int32_t* wh = (int32_t*)malloc(sizeof(int32_t) * 8);
+  const int32_t wh0[8] = {40, 40, 40, 40, 40, 32, 48, 32};
+  memcpy(wh, wh0, sizeof(wh0));
+  const struct { int B, n, C; } bad_ssd[] = {{0, 394, 5}, {-1, 394, 5}, {2, 0, 5}, {2, 4097, 5}, {2, -1, 5},
+                                             {2, 394, 4}, {2, 394, 0}, {2, 2147483647, 5}, {2, 394, -2147483647 - 1}};
+  for (const auto& s : bad_ssd)
+    wrong += tpg_ssd_landmarks(s.B, s.n, s.C, f, f, 0.5f, nullptr, wh, f, f, i32, i32, i32, nullptr) != -2;
+  wrong += tpg_ssd_landmarks(2, 394, 5, nullptr, f, 0.5f, nullptr, wh, f, f, i32, i32, i32, nullptr) != -10;
+  wrong += tpg_ssd_landmarks(2, 394, 5, f, nullptr, 0.5f, nullptr, wh, f, f, i32, i32, i32, nullptr) != -10;
+  wrong += tpg_ssd_landmarks(2, 394, 5, f, f, 0.5f, nullptr, nullptr, f, f, i32, i32, i32, nullptr) != -10;
+  wrong += tpg_ssd_landmarks(2, 394, 5, f, f, 0.5f, nullptr, wh, nullptr, f, i32, i32, i32, nullptr) != -10;
+  wrong += tpg_ssd_landmarks(2, 394, 5, f, f, 0.5f, nullptr, wh, f, nullptr, i32, i32, i32, nullptr) != -10;
+  wrong += tpg_ssd_landmarks(2, 394, 5, f, f, 0.5f, nullptr, wh, f, f, nullptr, i32, i32, nullptr) != -10;
+  wrong += tpg_ssd_landmarks(2, 394, 5, f, f, 0.5f, nullptr, wh, f, f, i32, nullptr, i32, nullptr) != -10;
+  wrong += tpg_ssd_landmarks(2, 394, 5, f, f, 0.5f, nullptr, wh, f, f, i32, i32, nullptr, nullptr) != -10;
+  wrong += tpg_ssd_landmarks(2, 394, 5, (float*)((char*)f + 2), f, 0.5f, nullptr, wh, f, f, i32, i32, i32, nullptr) == 0;
+  for (int k = 0; k < 8; ++k) {  // a patch side of zero or below
+    wh[k] = k % 2 ? 0 : -40;
+    wrong += tpg_ssd_landmarks(2, 394, 5, f, f, 0.5f, f, wh, f, f, i32, i32, i32, nullptr) != -2;
+    wh[k] = wh0[k];
+  }
+  free(wh);
+  for (int nb = 1; nb <= TPG_LM_MAX_BANDS; ++nb) {  // exact-size band tables, every valid count; B is bad
+    float* thr = (float*)malloc(sizeof(float) * nb);
+    float* wgt = (float*)malloc(sizeof(float) * nb);
+    for (int i = 0; i < nb; ++i) { thr[i] = 5.f * (i + 1); wgt[i] = 1.f / (i + 1); }
+    wrong += tpg_landmark_accuracy(0, f, f, nullptr, nb, thr, wgt, f, nullptr) != -2;
+    wrong += tpg_landmark_accuracy(-3, f, f, i32, nb, thr, wgt, f, nullptr) != -2;
+    wrong += tpg_landmark_accuracy(4, nullptr, f, nullptr, nb, thr, wgt, f, nullptr) != -10;
+    wrong += tpg_landmark_accuracy(4, f, nullptr, nullptr, nb, thr, wgt, f, nullptr) != -10;
+    wrong += tpg_landmark_accuracy(4, f, f, nullptr, nb, nullptr, wgt, f, nullptr) != -10;
+    wrong += tpg_landmark_accuracy(4, f, f, nullptr, nb, thr, nullptr, f, nullptr) != -10;
+    wrong += tpg_landmark_accuracy(4, f, f, nullptr, nb, thr, wgt, nullptr, nullptr) != -10;
+    if (nb > 1) {  // descending, and a NaN edge
+      thr[nb - 1] = thr[0] - 1.f;
+      wrong += tpg_landmark_accuracy(4, f, f, nullptr, nb, thr, wgt, f, nullptr) != -2;
+      thr[nb - 1] = __builtin_nanf("");
+      wrong += tpg_landmark_accuracy(4, f, f, nullptr, nb, thr, wgt, f, nullptr) != -2;
+    }
+    thr[0] = -1.f;  // below the implied lower edge 0
+    wrong += tpg_landmark_accuracy(4, f, f, nullptr, nb, thr, wgt, f, nullptr) != -2;
+    // a band count outside 1..8 is refused before either table is read
+    const int bad_nb[] = {0, 9, -1, 2147483647, -2147483647 - 1};
+    for (int b : bad_nb) wrong += tpg_landmark_accuracy(4, f, f, nullptr, b, thr, wgt, f, nullptr) != -2;
+    free(thr);
+    free(wgt);
+  }
+  tpg_tensor out, nul, badt;
+  memset(&out, 0, sizeof(out));
+  out.data = f; out.dtype = TPG_BF16;
+  out.stride[0] = 128 * 128 * 8; out.stride[1] = 1; out.stride[2] = 128 * 8; out.stride[3] = 8;
+  nul = out; nul.data = nullptr;
+  badt = out; badt.dtype = 5;
+  int64_t* is = (int64_t*)malloc(sizeof(int64_t) * 4);
+  is[0] = 128 * 128 * 3; is[1] = 1; is[2] = 128 * 3; is[3] = 3;
+  const int bad_dim[] = {0, -1, -2147483647 - 1};
+  for (int v : bad_dim) {
+    wrong += tpg_u8_to_unit(v, 3, 128, 128, u8, is, out, nullptr) != -2;
+    wrong += tpg_u8_to_unit(2, v, 128, 128, u8, is, out, nullptr) != -2;
+    wrong += tpg_u8_to_unit(2, 3, v, 128, u8, is, out, nullptr) != -2;
+    wrong += tpg_u8_to_unit(2, 3, 128, v, u8, is, out, nullptr) != -2;
+  }
+  wrong += tpg_u8_to_unit(32768, 3, 256, 256, u8, is, out, nullptr) != -2;  // 2^31 pixels
+  wrong += tpg_u8_to_unit(2147483647, 3, 2147483647, 2147483647, u8, is, out, nullptr) != -2;
+  wrong += tpg_u8_to_unit(2, 3, 128, 128, nullptr, is, out, nullptr) != -10;
+  wrong += tpg_u8_to_unit(2, 3, 128, 128, u8, nullptr, out, nullptr) != -10;
+  wrong += tpg_u8_to_unit(2, 3, 128, 128, u8, is, nul, nullptr) != -10;
+  wrong += tpg_u8_to_unit(2, 3, 128, 128, u8, is, badt, nullptr) == 0;
+  free(is);
+  if (wrong) { fprintf(stderr, "landmark front end: %d malformed calls not refused as documented\n", wrong); g_fail = 1; }
+}
+
 static tpg_conv_desc conv(int n, int ci, int h, int w, int co, int k, int s, int p, int dt, bool T = false,
                           int op_pad = 0, int pm = TPG_PAD_ZERO) {
   tpg_conv_desc d;
@@ -524,6 +607,7 @@ int main(int argc, char** argv) {
   }
   resize_jobs();
   identity_sweep(iters < 2000 ? iters : 2000);
+  landmark_sweep();
   printf("planner_asan: %ld valid, %ld rejected descriptors, %ld pack jobs, %ld wgrad plans, %ld data plans, "
          "%ld resize tables, %ld top-k plans, %s\n", g_valid, g_rejected, g_jobs, g_plans, g_dplans, g_tables, g_idplans,
          g_fail ? "FAILED" : "ok");

@@ -18,6 +18,8 @@ Device path (no per-sample Python, no host synchronisation unless `check=True`):
     a batch of RGB images of different sizes, byte for byte, in two launches (tpg_resize_u8).
   FaceBatcher.from_raw(imgs, lm68) -> the whole of TestDataset.__getitem__ for a batch of raw
     photos (TestDataset(raw=True)): resize to 128, landmark rescale, crops, 64 / 32 images.
+  FaceBatcher.from_points(u8_128, boxes) -> the same dict from crop boxes already on the device
+    (tpgan_ops.ssd_landmarks: the landmark detector's points instead of 68 given landmarks).
 
 The reference's five-point table ends with [68, 68] (UtilityMethods.py:148), past the 68
 landmarks: the mouth's right corner is NaN and math.floor raises ValueError in process(), so
@@ -372,4 +374,23 @@ class FaceBatcher:
         out["I64"] = self.normalize(u64, "I64")
         out["I32"] = self.normalize(self.resize(u64, (32, 32)), "I32")
         out["u8_128"] = u8
+        return out
+
+    def from_points(self, u8_128, boxes):
+        """from_raw's result from crop boxes that are already on the device (tpgan_ops.ssd_landmarks:
+        the landmark detector's four points): u8_128 uint8 [B, 128, 128, 3], boxes int32 [B, 4, 4]
+        (left, upper, right, lower) -> __call__'s dict plus "I64", "I32" and "u8_128"."""
+        self._rgb_u8(u8_128, "u8_128", 4)
+        B, H, W, C = u8_128.shape
+        if not isinstance(boxes, torch.Tensor) or boxes.dtype != torch.int32 or tuple(boxes.shape) != (B, 4, 4):
+            raise ValueError("boxes must be an int32 [%d, 4, 4] device tensor" % B)
+        self._on_device(boxes, "boxes")
+        boxes = boxes.contiguous()
+        jobs = [("I128", H, W, -1)] + [(n, PATCH_SIZE[n][1], PATCH_SIZE[n][0], i) for i, n in enumerate(PATCH_NAMES)]
+        out = self._crop(u8_128, jobs, boxes)
+        out["boxes"] = boxes
+        u64 = self.resize(u8_128, (64, 64))
+        out["I64"] = self.normalize(u64, "I64")
+        out["I32"] = self.normalize(self.resize(u64, (32, 32)), "I32")
+        out["u8_128"] = u8_128
         return out

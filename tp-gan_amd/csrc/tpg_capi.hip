@@ -1,6 +1,6 @@
 // C-ABI of libtpgan_hip.so (include/tpgan.h): the conv entry points validate, plan (tpg_plan.h)
-// and run the plan's launch sequence (run_data, run_wgrad); the losses, fuser, maxout, Adam and
-// SSD entry points validate and call their launcher.  Every entry point that launches calls
+// and run the plan's launch sequence (run_data, run_wgrad); the losses, fuser, maxout, Adam, SSD
+// and landmark-front-end entry points validate and call their launcher.  Every entry point that launches calls
 // group_sync() before its first launch and returns through hip_check / fail (tpg_internal.h).
 #include "tpg_plan.h"
 #include "../../include/tpgan.h"
@@ -612,4 +612,46 @@ extern "C" int32_t tpg_ssd_decode(int32_t B, int32_t n, int32_t C, const float* 
   if (!keep || !score) return fail(-10, "ssd_decode: NULL output");
   return hip_check(launch_ssd_decode(B, n, C, loc, cls, conf, nms_thr, top_k, keep, score, (hipStream_t)stream),
                    "ssd_decode");
+}
+
+// ---- landmark front end: top-1 decode + crop boxes, the banded accuracy (tpg_ssd.hip) and
+// ToTensor (tpg_data.hip)
+extern "C" int32_t tpg_ssd_landmarks(int32_t B, int32_t n, int32_t C, const float* loc, const float* cls, float conf,
+                                     const float* scale, const int32_t* patch_wh, float* points, float* score,
+                                     int32_t* anchor, int32_t* boxes, int32_t* status, tpg_stream_t stream) {
+  if (int32_t grc = group_sync()) return grc;
+  int32_t rc = check_ssd(B, n, C, loc, cls, "ssd_landmarks");
+  if (rc) return rc;
+  if (!patch_wh || !points || !score || !anchor || !boxes || !status) return fail(-10, "ssd_landmarks: NULL pointer");
+  if ((uintptr_t)scale % 4) return fail(-15, "ssd_landmarks: scale must be 4-byte aligned");
+  for (int i = 0; i < 8; ++i)
+    if (patch_wh[i] <= 0) return fail(-2, "ssd_landmarks: bad patch size");
+  return hip_check(launch_ssd_landmarks(B, n, C, loc, cls, conf, scale, patch_wh, points, score, anchor, boxes, status,
+                                        (hipStream_t)stream), "ssd_landmarks");
+}
+
+extern "C" int32_t tpg_landmark_accuracy(int32_t B, const float* pred, const float* truth, const int32_t* status,
+                                         int32_t nbands, const float* thresholds, const float* weights, float* acc,
+                                         tpg_stream_t stream) {
+  if (int32_t grc = group_sync()) return grc;
+  if (B < 1 || nbands < 1 || nbands > TPG_LM_MAX_BANDS)
+    return fail(-2, "landmark_accuracy: B %d, nbands %d (1..%d)", B, nbands, TPG_LM_MAX_BANDS);
+  if (!pred || !truth || !thresholds || !weights || !acc) return fail(-10, "landmark_accuracy: NULL pointer");
+  for (int i = 0; i < nbands; ++i)
+    if (!(thresholds[i] >= (i ? thresholds[i - 1] : 0.f)))
+      return fail(-2, "landmark_accuracy: thresholds must ascend from 0 (band %d)", i);
+  return hip_check(launch_landmark_accuracy(B, pred, truth, status, nbands, thresholds, weights, acc,
+                                            (hipStream_t)stream), "landmark_accuracy");
+}
+
+extern "C" int32_t tpg_u8_to_unit(int32_t n, int32_t c, int32_t h, int32_t w, const uint8_t* img,
+                                  const int64_t* img_stride, tpg_tensor out, tpg_stream_t stream) {
+  if (int32_t grc = group_sync()) return grc;
+  // (h * w first: the product of three 31-bit sizes does not fit 64 bits)
+  if (n < 1 || c < 1 || h < 1 || w < 1 || (int64_t)h * w > 0x7fffffffLL || (int64_t)h * w * n > 0x7fffffffLL)
+    return fail(-2, "u8_to_unit: bad sizes %d x %d x %d x %d", n, c, h, w);
+  if (!img || !img_stride || !out.data) return fail(-10, "u8_to_unit: NULL pointer");
+  if (out.dtype != TPG_F32 && out.dtype != TPG_BF16 && out.dtype != TPG_F16)
+    return fail(-11, "u8_to_unit: bad dtype %d", out.dtype);
+  return hip_check(launch_u8_to_unit(n, c, h, w, img, img_stride, out, (hipStream_t)stream), "u8_to_unit");
 }

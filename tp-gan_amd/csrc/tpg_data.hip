@@ -7,6 +7,8 @@
 //  crop_norm_kernel       PIL crop (zero outside the image) + ToTensor + x*2-1
 //                         (DataAndDataset.py:51-54, 216-220, 252-255) for up to 8 jobs
 //                         (4 patches + whole images) of a batch in one launch.
+//  u8_to_unit_kernel      ToTensor alone, u8 / 255 into [0, 1]: the landmark detector's input
+//                         (Pretrain.py trains on it), f32 / bf16 / f16, any output strides.
 //
 // Arithmetic follows the reference bit for bit: float32 row sums in index order divided by
 // the count (numpy's mean over axis 0 of a (k, 2) float32 array), float32 rescale and mouth
@@ -124,7 +126,51 @@ __global__ void crop_norm_kernel(CropArgs a) {
   }
 }
 
+// ToTensor(): u8 / 255 (IEEE division) into f32 / bf16 / f16, one thread per pixel
+struct UnitArgs {
+  const uint8_t* img;
+  int64_t is[4];  // element strides of the logical (n, c, h, w) u8 view
+  int32_t c, h, w;
+  int64_t npix;   // n * h * w
+  tpg_tensor out;
+};
+
+__global__ void u8_to_unit_kernel(UnitArgs a) {
+#pragma clang fp contract(off)
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= a.npix) return;
+  const int x = (int)(t % a.w), y = (int)(t / a.w % a.h);
+  const int64_t b = t / ((int64_t)a.w * a.h);
+  const uint8_t* src = a.img + b * a.is[0] + (int64_t)y * a.is[2] + (int64_t)x * a.is[3];
+  const int64_t o = b * a.out.stride[0] + (int64_t)y * a.out.stride[2] + (int64_t)x * a.out.stride[3];
+  for (int c = 0; c < a.c; ++c) {
+    const float v = (float)src[c * a.is[1]] / 255.0f;
+    const int64_t e = o + c * a.out.stride[1];
+    if (a.out.dtype == TPG_BF16)
+      reinterpret_cast<__hip_bfloat16*>(a.out.data)[e] = __float2bfloat16(v);
+    else if (a.out.dtype == TPG_F16)
+      reinterpret_cast<_Float16*>(a.out.data)[e] = (_Float16)v;
+    else
+      reinterpret_cast<float*>(a.out.data)[e] = v;
+  }
+}
+
 }  // namespace
+
+int launch_u8_to_unit(int n, int c, int h, int w, const uint8_t* img, const int64_t* img_stride, const tpg_tensor& out,
+                      hipStream_t s) {
+  UnitArgs a;
+  a.img = img;
+  for (int i = 0; i < 4; ++i) a.is[i] = img_stride[i];
+  a.c = c;
+  a.h = h;
+  a.w = w;
+  a.npix = (int64_t)n * h * w;
+  a.out = out;
+  hipLaunchKernelGGL(u8_to_unit_kernel, dim3((unsigned)((a.npix + 255) / 256)), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
+
 }  // namespace tpg
 
 using namespace tpg;

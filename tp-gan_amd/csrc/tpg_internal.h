@@ -587,6 +587,14 @@ int launch_ssd_loss_bwd(int B, int n, int C, const float* pred, const float* cls
                         const float* terms, const float* gout, float* dloc, float* dcls, hipStream_t s);
 int launch_ssd_decode(int B, int n, int C, const float* loc, const float* cls, float conf, float nms_thr, int top_k,
                       int* keep, float* score, hipStream_t s);
+// landmark front end: top-1 decode + crop boxes and the banded accuracy (tpg_ssd.hip), ToTensor (tpg_data.hip)
+int launch_ssd_landmarks(int B, int n, int C, const float* loc, const float* cls, float conf, const float* scale,
+                         const int* patch_wh, float* points, float* score, int* anchor, int* boxes, int* status,
+                         hipStream_t s);
+int launch_landmark_accuracy(int B, const float* pred, const float* truth, const int* status, int nbands,
+                             const float* thresholds, const float* weights, float* acc, hipStream_t s);
+int launch_u8_to_unit(int n, int c, int h, int w, const uint8_t* img, const int64_t* img_stride, const tpg_tensor& out,
+                      hipStream_t s);
 int launch_pack_halo(const PackArgs& a, int nks, int bn, int ntiles, hipStream_t s);
 // elementwise launchers behind the C entry points of the same names (tpg_elementwise.hip);
 // launch_adam / launch_grad_check: -1 for misaligned buffers, before any launch

@@ -19,6 +19,9 @@
 // ssd_decode: one block per (image, class): softmax confidence > threshold, sorted by score
 //   (then index), greedy suppression of the points within nms_thr (<=) of each kept one, the
 //   first top_k kept.
+// ssd_landmarks: one block per image: the best anchor of each of the four landmark classes (slot
+//   0 of ssd_decode with top_k = 1, no sort) and its crop box; landmark_accuracy: Pretrain.py's
+//   banded accuracy, one thread per image.
 #include "tpg_internal.h"
 #include <math.h>
 
@@ -292,6 +295,168 @@ __global__ __launch_bounds__(SSD_T) void ssd_decode_kernel(const SsdDecArgs a) {
     }
     __syncthreads();
   }
+}
+
+// ---- landmark front end: top-1 decode fused with process()'s crop boxes, and Pretrain.py's
+// banded accuracy.
+// ssd_landmarks: one block per image.  Each thread walks anchors tid, tid + SSD_T, ... with one
+//   ssd_lse per anchor and keeps, per landmark class, its best (score, index); the bests are
+//   combined across the wave with __shfl_xor, across the four waves through LDS.  "Better" is
+//   (score descending, index ascending) over the non-NaN scores with "none" as the identity: an
+//   associative, commutative order, so the result does not depend on the thread mapping.  The
+//   score is the decoder's own expression, expf(x[l] - ssd_lse(x, C)): bit-identical to slot 0 of
+//   ssd_decode with top_k = 1 (greedy NMS keeps exactly the best candidate).
+// landmark_accuracy: one thread per image.
+struct SsdBest {
+  float s;
+  int i;  // -1: none yet (every score so far was NaN)
+};
+
+__device__ __forceinline__ SsdBest ssd_better(SsdBest a, SsdBest b) {
+  const bool take_b = b.i >= 0 && (a.i < 0 || b.s > a.s || (b.s == a.s && b.i < a.i));
+  return take_b ? b : a;
+}
+
+struct SsdLmArgs {
+  int B, n, C;
+  const float* loc;    // (B, n, 2)
+  const float* cls;    // (B, n, C)
+  float conf;
+  const float* scale;  // (B, 2) or null
+  int pw[4], ph[4];    // patch (width, height): left_eye, right_eye, nose, mouth
+  float* points;       // (B, 4, 2)
+  float* score;        // (B, 4)
+  int* anchor;         // (B, 4)
+  int* boxes;          // (B, 4, 4)
+  int* status;         // (B)
+};
+
+__global__ __launch_bounds__(SSD_T) void ssd_landmarks_kernel(const SsdLmArgs a) {
+  constexpr int NW = SSD_T / 64;
+  __shared__ float ws[NW][4];
+  __shared__ int wi[NW][4];
+  __shared__ int sst[4];
+  const int b = blockIdx.x, n = a.n, tid = threadIdx.x;
+  const float* X = a.cls + (int64_t)b * n * a.C;
+  SsdBest best[4];
+  for (int l = 0; l < 4; ++l) best[l] = SsdBest{0.f, -1};
+  for (int i = tid; i < n; i += SSD_T) {
+    const float* x = X + (int64_t)i * a.C;
+    const float lse = ssd_lse(x, a.C);
+    for (int l = 0; l < 4; ++l) {
+      const float s = expf(x[l] - lse);
+      if (s == s) best[l] = ssd_better(best[l], SsdBest{s, i});
+    }
+  }
+  for (int l = 0; l < 4; ++l) {
+    for (int off = 32; off > 0; off >>= 1) {
+      SsdBest o;
+      o.s = __shfl_xor(best[l].s, off, 64);
+      o.i = __shfl_xor(best[l].i, off, 64);
+      best[l] = ssd_better(best[l], o);
+    }
+    if ((tid & 63) == 0) {
+      ws[tid >> 6][l] = best[l].s;
+      wi[tid >> 6][l] = best[l].i;
+    }
+  }
+  __syncthreads();
+  if (tid < 4) {
+#pragma clang fp contract(off)
+    const int l = tid;
+    SsdBest r{ws[0][l], wi[0][l]};
+    for (int w = 1; w < NW; ++w) r = ssd_better(r, SsdBest{ws[w][l], wi[w][l]});
+    int st = (r.i >= 0 && r.s > a.conf) ? 0 : (1 << l);
+    float pt[2] = {__builtin_nanf(""), __builtin_nanf("")};
+    if (r.i >= 0) {
+      const float* P = a.loc + ((int64_t)b * n + r.i) * 2;
+      pt[0] = P[0];
+      pt[1] = P[1];
+      if (a.scale) {
+        pt[0] = pt[0] * a.scale[2 * b];
+        pt[1] = pt[1] * a.scale[2 * b + 1];
+      }
+    }
+    const int64_t o = (int64_t)b * 4 + l;
+    a.points[2 * o] = pt[0];
+    a.points[2 * o + 1] = pt[1];
+    a.score[o] = r.i >= 0 ? r.s : 0.f;
+    a.anchor[o] = r.i;
+    // the crop box of process() (DataAndDataset.py:42-54), as landmark_boxes_kernel
+    int xy[2];
+    for (int d = 0; d < 2; ++d) {
+      const float v = pt[d];
+      if (!(v == v) || fabsf(v) > 1.0e9f) {
+        st |= 16;
+        xy[d] = 0;
+      } else {
+        xy[d] = (int)floorf(v);
+      }
+    }
+    int* bx = a.boxes + 4 * o;
+    bx[0] = xy[0] - a.pw[l] / 2 + 1;
+    bx[1] = xy[1] - a.ph[l] / 2 + 1;
+    bx[2] = xy[0] + a.pw[l] / 2 + 1;
+    bx[3] = xy[1] + a.ph[l] / 2 + 1;
+    sst[l] = st;
+  }
+  __syncthreads();
+  if (tid == 0) a.status[b] = sst[0] | sst[1] | sst[2] | sst[3];
+}
+
+struct SsdAccArgs {
+  int B, nbands;
+  const float* pred;   // (B, 4, 2)
+  const float* truth;  // (B, 4, 2)
+  const int* status;   // (B) or null
+  float thr[TPG_LM_MAX_BANDS], wgt[TPG_LM_MAX_BANDS];
+  float* acc;          // (B)
+};
+
+__global__ void landmark_accuracy_kernel(const SsdAccArgs a) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= a.B) return;
+  const float* P = a.pred + (int64_t)b * 8;
+  const float* T = a.truth + (int64_t)b * 8;
+  const int st = a.status ? a.status[b] : 0;
+  float sum = 0.f;
+  for (int l = 0; l < 4; ++l) {
+    const float dx = P[2 * l] - T[2 * l], dy = P[2 * l + 1] - T[2 * l + 1];
+    const float d = sqrtf(dx * dx + dy * dy);
+    // (prev, thr] bands from 0: d == 0 and a NaN d fall in none (Pretrain.py:49-59)
+    float sc = 0.f, prev = 0.f;
+    for (int i = 0; i < a.nbands; ++i) {
+      if (d > prev && d <= a.thr[i]) sc = sc + a.wgt[i];
+      prev = a.thr[i];
+    }
+    if ((st >> l) & 1) sc = 0.f;
+    sum = sum + sc;
+  }
+  a.acc[b] = sum / 4.0f;
+}
+
+int launch_ssd_landmarks(int B, int n, int C, const float* loc, const float* cls, float conf, const float* scale,
+                         const int* patch_wh, float* points, float* score, int* anchor, int* boxes, int* status,
+                         hipStream_t s) {
+  SsdLmArgs a{B, n, C, loc, cls, conf, scale, {}, {}, points, score, anchor, boxes, status};
+  for (int i = 0; i < 4; ++i) {
+    a.pw[i] = patch_wh[2 * i];
+    a.ph[i] = patch_wh[2 * i + 1];
+  }
+  hipLaunchKernelGGL(ssd_landmarks_kernel, dim3(B), dim3(SSD_T), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+int launch_landmark_accuracy(int B, const float* pred, const float* truth, const int* status, int nbands,
+                             const float* thresholds, const float* weights, float* acc, hipStream_t s) {
+  SsdAccArgs a{B, nbands, pred, truth, status, {}, {}, acc};
+  for (int i = 0; i < nbands; ++i) {
+    a.thr[i] = thresholds[i];
+    a.wgt[i] = weights[i];
+  }
+  hipLaunchKernelGGL(landmark_accuracy_kernel, dim3((B + 63) / 64), dim3(64), 0, s, a);
+  return (int)hipGetLastError();
 }
 
 static size_t ssd_fwd_lds(int n) {

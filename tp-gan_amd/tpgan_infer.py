@@ -9,6 +9,10 @@ uint8 frontal faces, and PSNR / SSIM against the ground-truth frontal view.
     ids.enroll(gallery_u8, labels)                           # frontal views, one label each
     hit = ids.identify(fz(imgs, lm68), k=5)                  # idx, score, label [B, 5]
     cmc = ids.cmc(true_labels, hit)                          # rank-1 .. rank-5 rates
+    det = LandmarkDetector.from_checkpoint("pretrain_ckpt")  # a trained MobileNetV2 + SSD head
+    fz = Frontalizer(G, detector=det)
+    u8 = fz(imgs)                                            # no landmarks supplied
+    d = det.detect(imgs)                                     # points, score, boxes, status, ...
 
 The data path is FaceBatcher.from_raw (Pillow-exact LANCZOS, landmark crops, [-1, 1]), the
 model is the product's Generator frozen in eval mode, the way back to pixels is
@@ -20,6 +24,11 @@ TP-GAN is judged on identity, not pixels: IdentityScorer turns u8 faces into uni
 embeddings of a frozen FeatureExtract.FeatureExtractModel (tpgan_ops.l2_normalize), keeps a
 device-resident gallery of them and finds each probe's best matches with tpgan_ops.cosine_topk,
 which never builds the probes x gallery similarity matrix.
+
+Without landmarks, LandmarkDetector finds the four crop centres itself: LANCZOS resize,
+tpgan_ops.u8_to_unit ([0, 1], what the detector was trained on), the MobileNetV2 + SSD head, and
+tpgan_ops.ssd_landmarks, which decodes the head's outputs straight into FaceBatcher.from_points'
+crop boxes.  One status word per face is the only thing read back.
 """
 import os
 import re
@@ -44,6 +53,28 @@ def _check_state_dict(own, sd, what):
             raise ValueError("%s: %s has shape %s, model %s" % (what, k, tuple(v.shape), tuple(own[k].shape)))
 
 
+def _u8_images(device, imgs, name):
+    """A [B, H, W, 3] tensor or a list of [H_i, W_i, 3] arrays / tensors -> the same on the device."""
+    def one(t, what, dim):
+        t = torch.as_tensor(np.ascontiguousarray(t) if isinstance(t, np.ndarray) else t)
+        if t.dtype != torch.uint8 or t.dim() != dim or t.shape[-1] != 3:
+            raise ValueError("%s must be uint8 %s" % (what, "[B, H, W, 3]" if dim == 4 else "[H, W, 3]"))
+        return t.to(device).contiguous()
+    if isinstance(imgs, (torch.Tensor, np.ndarray)) and imgs.ndim == 4:
+        return one(imgs, name, 4)
+    return [one(t, "%s[%d]" % (name, i), 3) for i, t in enumerate(imgs)]
+
+
+def _photo_wh(imgs):
+    """float64 [B, 2] (width, height) of _u8_images' result."""
+    if isinstance(imgs, torch.Tensor):
+        return np.array([[imgs.shape[2], imgs.shape[1]]] * imgs.shape[0], np.float64).reshape(-1, 2)
+    return np.array([[t.shape[1], t.shape[0]] for t in imgs], np.float64).reshape(-1, 2)
+
+
+_NAN_POINT = "cannot convert float NaN to integer: a landmark point of face(s) %s is NaN or infinite"
+
+
 class Frontalizer:
     """A frozen Generator behind a photo-in, pixels-out interface.
 
@@ -53,9 +84,11 @@ class Frontalizer:
                     a call), and its packed weight images keep following the optimizer.
     compute_dtype   torch.bfloat16 (default), torch.float16 or torch.float32.
     max_batch       faces per forward pass of __call__ / frontalize_batch.
+    detector        a LandmarkDetector on the same device, or None.  With one, __call__ and evaluate
+                    take lm68=None: the detector's four points are the crop centres.
     """
 
-    def __init__(self, G, device="cuda", compute_dtype=torch.bfloat16, max_batch=32):
+    def __init__(self, G, device="cuda", compute_dtype=torch.bfloat16, max_batch=32, detector=None):
         if compute_dtype not in (torch.float32, torch.bfloat16, torch.float16):
             raise ValueError("compute_dtype must be float32, bfloat16 or float16, got %s" % compute_dtype)
         if int(max_batch) < 1:
@@ -65,6 +98,12 @@ class Frontalizer:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.compute_dtype = compute_dtype
         self.max_batch = int(max_batch)
+        if detector is not None:
+            if not isinstance(detector, LandmarkDetector):
+                raise ValueError("detector must be a LandmarkDetector or None, got %s" % type(detector).__name__)
+            if detector.device != self.device:
+                raise ValueError("detector is on %s, the Frontalizer on %s" % (detector.device, self.device))
+        self.detector = detector
         self.G = G
         self.zdim = G.global_pathway.zdim
         self.img_size = G.img_size
@@ -130,15 +169,7 @@ class Frontalizer:
         return z.to(self.device, torch.float32)
 
     def _u8_images(self, imgs, name):
-        """A [B, H, W, 3] tensor or a list of [H_i, W_i, 3] arrays / tensors -> the same on the device."""
-        def one(t, what, dim):
-            t = torch.as_tensor(np.ascontiguousarray(t) if isinstance(t, np.ndarray) else t)
-            if t.dtype != torch.uint8 or t.dim() != dim or t.shape[-1] != 3:
-                raise ValueError("%s must be uint8 %s" % (what, "[B, H, W, 3]" if dim == 4 else "[H, W, 3]"))
-            return t.to(self.device).contiguous()
-        if isinstance(imgs, (torch.Tensor, np.ndarray)) and imgs.ndim == 4:
-            return one(imgs, name, 4)
-        return [one(t, "%s[%d]" % (name, i), 3) for i, t in enumerate(imgs)]
+        return _u8_images(self.device, imgs, name)
 
     def _batcher(self):
         if self._fb is None:
@@ -170,14 +201,29 @@ class Frontalizer:
                  for s in range(0, B, self.max_batch)]
         return torch.cat(parts)
 
-    def __call__(self, imgs, lm68, z=None):
+    def __call__(self, imgs, lm68=None, z=None):
         """imgs: uint8 photos, a list of [H_i, W_i, 3] (any mix of sizes) or one [B, H, W, 3];
-        lm68: float32 [B, 68, 2] landmarks in each photo's own pixels -> uint8 [B, 128, 128, 3]."""
+        lm68: float32 [B, 68, 2] landmarks in each photo's own pixels, or None with a detector
+        attached (its four points are the crop centres) -> uint8 [B, 128, 128, 3]."""
         if self.img_size != 128:
             raise ValueError("raw photos go through FaceBatcher.from_raw, which is 128-only; this generator "
                              "has img_size %d (use frontalize_batch)" % self.img_size)
+        if lm68 is None and self.detector is None:
+            raise ValueError("lm68 is None and no detector is attached (Frontalizer(G, detector=...))")
         imgs = self._u8_images(imgs, "imgs")
         B = len(imgs)
+        if lm68 is None:
+            z = self._z(z, B)
+            out = torch.empty(B, 128, 128, 3, dtype=torch.uint8, device=self.device)
+            if B == 0:
+                return out
+            # every face's landmarks first: nothing is returned for a batch with a bad one
+            d = self.detector.detect(imgs)
+            fb = self._batcher()
+            for s in range(0, B, self.max_batch):
+                e = min(B, s + self.max_batch)
+                out[s:e] = self._forward_u8(fb.from_points(d["u8_128"][s:e], d["boxes"][s:e]), z[s:e])
+            return out
         lm68 = torch.as_tensor(lm68)
         if lm68.dtype != torch.float32 or lm68.dim() != 3 or lm68.shape[0] != B or lm68.shape[2] != 2:
             raise ValueError("lm68 must be float32 [%d, npts, 2]" % B)
@@ -193,8 +239,7 @@ class Frontalizer:
         status = fb.landmark_boxes(lm68, scale)[2]
         bad = torch.nonzero(status != 0).flatten().tolist()
         if bad:
-            raise ValueError("cannot convert float NaN to integer: a landmark point of face(s) %s is NaN or "
-                             "infinite" % bad)
+            raise ValueError(_NAN_POINT % bad)
         for s in range(0, B, self.max_batch):
             e = min(B, s + self.max_batch)
             out[s:e] = self._forward_u8(fb.from_raw(imgs[s:e], lm68[s:e]), z[s:e])
@@ -203,7 +248,7 @@ class Frontalizer:
     def evaluate(self, imgs, lm68, frontal, z=None, identity=None):
         """Frontalise and score against the ground-truth frontal view (uint8 [B, 128, 128, 3] on the
         device, or a list of raw photos, resized like the inputs) -> {"fake_u8", "sse" int64 [B],
-        "psnr" float64 [B] (inf where sse is 0), "ssim" float32 [B]}.  With identity=an
+        "psnr" float64 [B] (inf where sse is 0), "ssim" float32 [B]}.  lm68 as __call__.  With identity=an
         IdentityScorer the dict also holds "id_cos" float32 [B]: the cosine similarity of the
         identity embeddings of the frontalised face and of the true frontal view."""
         if identity is not None and not isinstance(identity, IdentityScorer):
@@ -381,3 +426,142 @@ class IdentityScorer:
             raise ValueError("no probes")
         hit = (label == probe_labels[:, None]) & (result["idx"] >= 0)
         return (hit.cumsum(1) > 0).to(torch.float64).mean(0)
+
+
+LANDMARK_NAMES = ("left_eye", "right_eye", "nose", "mouth")
+
+
+class LandmarkDetector:
+    """The landmark detector of the pretraining (MobileNetV2 + SSD head, Pretrain.py) as the
+    generator's front end: raw photos -> the left eye, right eye, nose and mouth centre, the four
+    crop centres of process(), and their crop boxes, with nothing leaving the device but one status
+    word per face.
+
+    model                 a MobileNetV2.MobileNetV2.  It is moved to `device`, frozen and put in eval
+                          mode; BatchNorm is folded once and the 16-bit weight images are packed once
+                          (tpgan_ops._FrozenPack), again only after load_state_dict.
+    compute_dtype         torch.bfloat16 (default), torch.float16 or torch.float32: the detector's
+                          arithmetic.  The decode is float32 throughout.
+    max_batch             faces per detector pass.
+    confidence_threshold  a landmark is found when its best softmax score is > this (MultiTaskDecoder's
+                          rule and default).
+    detect_hw             (height, width) the detector sees; the photos are resized to 128 x 128 first
+                          (the frame the generator's crops live in), then to this size when it differs.
+    on_missing            "raise": a face with a landmark that was not found fails the whole batch;
+                          "best": the best-scoring anchor is used all the same and "status" says so.
+    """
+
+    def __init__(self, model, device="cuda", compute_dtype=torch.bfloat16, max_batch=32, confidence_threshold=0.5,
+                 detect_hw=(128, 128), on_missing="raise"):
+        if compute_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError("compute_dtype must be float32, bfloat16 or float16, got %s" % compute_dtype)
+        if int(max_batch) < 1:
+            raise ValueError("max_batch must be >= 1, got %s" % max_batch)
+        if on_missing not in ("raise", "best"):
+            raise ValueError("on_missing must be 'raise' or 'best', got %r" % (on_missing,))
+        if not hasattr(model, "ssd_head") or not hasattr(model, "extra_layers"):
+            raise ValueError("model must be a MobileNetV2.MobileNetV2, got %s" % type(model).__name__)
+        detect_hw = (int(detect_hw[0]), int(detect_hw[1]))
+        if not (32 <= detect_hw[0] <= 4096 and 32 <= detect_hw[1] <= 4096):
+            raise ValueError("detect_hw sides must be in 32..4096, got %s" % (detect_hw,))
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.compute_dtype = compute_dtype
+        self.max_batch = int(max_batch)
+        self.confidence_threshold = float(confidence_threshold)
+        self.detect_hw = detect_hw
+        self.on_missing = on_missing
+        self.model = model.to(self.device).eval()
+        for p in self.model.parameters():
+            p.requires_grad_(False)
+        self._new_packs()
+        self._fb = None
+
+    def _new_packs(self):
+        # a fresh holder per parameter: the folded weights and their images are made on first use
+        for p in self.model.parameters():
+            p._tpg_flat = tpgan_ops._FrozenPack()
+
+    @classmethod
+    def from_checkpoint(cls, path, epoch=None, **kw):
+        """path: a .pth written by UtilityMethods.save_model (a bare state_dict), or the directory
+        the pretraining writes model_epoch_<epoch>.pth into (epoch=None: the largest integer epoch
+        there).  Loaded with weights_only=True; keys and shapes are checked before a model is touched."""
+        import MobileNetV2 as MN
+        if os.path.isdir(path):
+            if epoch is None:
+                found = [int(m.group(1)) for m in (re.fullmatch(r"model_epoch_(\d+)\.pth", f)
+                                                   for f in os.listdir(path)) if m]
+                if not found:
+                    raise ValueError("no model_epoch_<epoch>.pth under %s" % path)
+                epoch = max(found)
+            path = os.path.join(path, "model_epoch_%s.pth" % epoch)
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        model = MN.MobileNetV2()
+        _check_state_dict(model.state_dict(), sd, "checkpoint %s" % path)
+        model.load_state_dict(sd)
+        return cls(model, **kw)
+
+    def load_state_dict(self, sd):
+        """New weights (checked before anything changes); BatchNorm is folded and the images packed anew."""
+        _check_state_dict(self.model.state_dict(), sd, "load_state_dict")
+        self.model.load_state_dict(sd)  # in place: the parameters keep their storage
+        self._new_packs()
+
+    def _batcher(self):
+        if self._fb is None:
+            self._fb = FaceBatcher(self.device, dtype=torch.float32, check=False)
+        return self._fb
+
+    def _head(self, u8):
+        """uint8 [b, h, w, 3] at detect_hw -> the head's (locations, classifications) in float32."""
+        with tpgan_ops.compute_dtype(self.compute_dtype):
+            loc, cls = self.model(tpgan_ops.u8_to_unit(u8, self.compute_dtype))
+        return loc.float(), cls.float()
+
+    def detect(self, imgs):
+        """imgs: uint8 photos, a list of [H_i, W_i, 3] (any mix of sizes) or one [B, H, W, 3] ->
+        {"points" float32 [B, 4, 2] (x, y) of the left eye, right eye, nose and mouth centre in the
+        128 x 128 frame, "points_photo" the same in each photo's own pixels (times float32 (W / 128,
+        H / 128)), "score" float32 [B, 4], "anchor" int32 [B, 4], "boxes" int32 [B, 4, 4] (left, upper,
+        right, lower: FaceBatcher.from_points takes them), "status" int32 [B] (tpgan_ops.ssd_landmarks),
+        "u8_128" uint8 [B, 128, 128, 3]}.  The status read is the call's only copy to the host."""
+        imgs = _u8_images(self.device, imgs, "imgs")
+        B = len(imgs)
+        if B == 0:
+            raise ValueError("imgs holds no photos")
+        fb = self._batcher()
+        dh, dw = self.detect_hw
+        with torch.no_grad(), torch.cuda.device(self.device):
+            u8_128 = fb.resize(imgs, (128, 128))
+            u8_det = u8_128 if (dh, dw) == (128, 128) else fb.resize(u8_128, (dh, dw))
+            heads = [self._head(u8_det[s:s + self.max_batch]) for s in range(0, B, self.max_batch)]
+            loc = heads[0][0] if len(heads) == 1 else torch.cat([h[0] for h in heads])
+            cls = heads[0][1] if len(heads) == 1 else torch.cat([h[1] for h in heads])
+            if loc.shape[1] > 4096:
+                raise ValueError("detect_hw %s gives %d anchors; the decode takes at most 4096" %
+                                 (self.detect_hw, loc.shape[1]))
+            scale = None
+            if (dh, dw) != (128, 128):
+                one = (128.0 / np.array([dw, dh], np.float64)).astype(np.float32)
+                scale = torch.from_numpy(np.tile(one, (B, 1))).to(self.device)
+            points, score, anchor, boxes, status = tpgan_ops.ssd_landmarks(loc, cls, self.confidence_threshold, scale)
+            to_photo = torch.from_numpy((_photo_wh(imgs) / 128.0).astype(np.float32)).to(self.device)
+            points_photo = points * to_photo[:, None, :]
+            st = status.tolist()  # the one device-to-host copy
+        bad = [i for i, v in enumerate(st) if v & 16]
+        if bad:
+            raise ValueError(_NAN_POINT % bad)
+        if self.on_missing == "raise":
+            missing = {i: [LANDMARK_NAMES[l] for l in range(4) if v >> l & 1] for i, v in enumerate(st) if v & 15}
+            if missing:
+                raise ValueError("no anchor above confidence %g for face(s) %s: %s" %
+                                 (self.confidence_threshold, sorted(missing),
+                                  ", ".join("%d: %s" % (i, "/".join(missing[i])) for i in sorted(missing))))
+        return {"points": points, "points_photo": points_photo, "score": score, "anchor": anchor, "boxes": boxes,
+                "status": status, "u8_128": u8_128}
+
+    def accuracy(self, points, truth, status=None):
+        """Pretrain.py's banded accuracy per face, float32 [B] (tpgan_ops.landmark_accuracy)."""
+        return tpgan_ops.landmark_accuracy(points, truth, status)

@@ -20,6 +20,7 @@ if os.environ.get("TPG_LIB_PATH"):  # A/B builds of the same library (tools/ onl
 TPG_F32, TPG_BF16, TPG_F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_RELU6 = 0, 1, 2, 3
 SSD_TERMS, SSD_MAXN = 16, 4096  # (include/tpgan.h TPG_SSD_TERMS / TPG_SSD_MAXN)
+LM_MAX_BANDS = 8  # (TPG_LM_MAX_BANDS)
 PAD_ZERO, PAD_REFLECT = 0, 1
 OP_FWD, OP_BWD_DATA, OP_BWD_FILTER, OP_BWD_DATA_MASKED = 0, 1, 2, 3
 
@@ -178,6 +179,12 @@ EXPORTS = {
                          [ctypes.c_void_p] * 7),
     "tpg_ssd_decode": (ctypes.c_int32, [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 2 + [ctypes.c_float] * 2 +
                        [ctypes.c_int32] + [ctypes.c_void_p] * 3),
+    "tpg_ssd_landmarks": (ctypes.c_int32, [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 2 + [ctypes.c_float] +
+                          [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)] + [ctypes.c_void_p] * 6),
+    "tpg_landmark_accuracy": (ctypes.c_int32, [ctypes.c_int32] + [ctypes.c_void_p] * 3 + [ctypes.c_int32] +
+                              [ctypes.POINTER(ctypes.c_float)] * 2 + [ctypes.c_void_p] * 2),
+    "tpg_u8_to_unit": (ctypes.c_int32, [ctypes.c_int32] * 4 + [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+                                                               TpgTensor, ctypes.c_void_p]),
     "tpg_set_deterministic": (None, [ctypes.c_int32]),
     "tpg_group_begin": (None, []),
     "tpg_group_member": (None, []),

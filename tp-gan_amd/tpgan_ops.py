@@ -19,9 +19,9 @@ import weakref
 
 import torch
 
-from tpgan_lib import (ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_RELU6, FLAG_CONCURRENT, FLAG_DX_ACCUM, FLAG_WPACKED, OP_BWD_DATA, OP_FWD,
-                       PAD_REFLECT,
-                       PAD_ZERO, SSD_TERMS, TPG_BF16, TPG_F32, ConvDesc, TpgTensor, check, dtype_code, dtype_from_code,
+from tpgan_lib import (ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_RELU6, FLAG_CONCURRENT, FLAG_DX_ACCUM, FLAG_WPACKED, LM_MAX_BANDS,
+                       OP_BWD_DATA, OP_FWD, PAD_REFLECT,
+                       PAD_ZERO, SSD_MAXN, SSD_TERMS, TPG_BF16, TPG_F32, ConvDesc, TpgTensor, check, dtype_code, dtype_from_code,
                        load, stream_ptr, tt)
 
 _DTYPE = [torch.float32]
@@ -2106,6 +2106,127 @@ def ssd_decode(loc, cls, conf, nms_thr, top_k):
     check(lib.tpg_ssd_decode(B, n, C, loc.data_ptr(), cls.data_ptr(), float(conf), float(nms_thr), int(top_k),
                              keep.data_ptr(), score.data_ptr(), stream_ptr()))
     return keep, score
+
+
+# ---- landmark front end (tpg_ssd.hip, tpg_data.hip): the detector's head outputs -> the four crop
+# centres and PIL crop boxes with nothing leaving the device, ToTensor for the detector's input
+# and Pretrain.py's banded accuracy.  None is differentiable.
+_LM_PATCH_WH = (ctypes.c_int32 * 8)(40, 40, 40, 40, 40, 32, 48, 32)  # (w, h): DataAndDataset.PATCH_SIZE
+
+
+def _lm_arg(fn, name, t, shape_txt, ok):
+    if not isinstance(t, torch.Tensor) or not ok(t):
+        raise ValueError("%s: %s must be a float32 %s tensor" % (fn, name, shape_txt))
+    if not t.is_cuda:
+        raise ValueError("%s: %s must be a device tensor, got a %s tensor" % (fn, name, t.device))
+
+
+def ssd_landmarks(loc, cls, conf, scale=None):
+    """Top-1 decode of the SSD landmark head fused with process()'s crop boxes (tpg_ssd_landmarks).
+    loc float32 [B, n, 2] pixel locations, cls float32 [B, n, C] logits (C >= 5, class 4 background,
+    n <= 4096), scale float32 [B, 2] (sx, sy) or None -> (points float32 [B, 4, 2], score float32
+    [B, 4], anchor int32 [B, 4], boxes int32 [B, 4, 4] (left, upper, right, lower), status int32
+    [B]).  Per landmark class the anchor of the largest softmax score (the lowest index among equal
+    scores; slot 0 of ssd_decode with top_k = 1 where that finds one); status bit l: landmark l's
+    best score is not > conf, bit 4 (16): a chosen coordinate is NaN or infinite."""
+    fn = "ssd_landmarks"
+    _lm_arg(fn, "loc", loc, "[B, n, 2]", lambda t: t.dtype == torch.float32 and t.dim() == 3 and t.shape[2] == 2)
+    _lm_arg(fn, "cls", cls, "[B, n, C]", lambda t: t.dtype == torch.float32 and t.dim() == 3)
+    B, n, C = cls.shape
+    if tuple(loc.shape[:2]) != (B, n) or loc.device != cls.device:
+        raise ValueError("%s: loc %s on %s and cls %s on %s must match" %
+                         (fn, tuple(loc.shape), loc.device, tuple(cls.shape), cls.device))
+    if B < 1 or not 1 <= n <= SSD_MAXN:
+        raise ValueError("%s: B >= 1 and 1..%d anchors, got B %d, n %d" % (fn, SSD_MAXN, B, n))
+    if C < 5:
+        raise ValueError("%s: C >= 5 classes (four landmarks and the background), got %d" % (fn, C))
+    if scale is not None:
+        _lm_arg(fn, "scale", scale, "[B, 2]", lambda t: t.dtype == torch.float32 and tuple(t.shape) == (B, 2))
+        if scale.device != cls.device:
+            raise ValueError("%s: scale must be on %s, got %s" % (fn, cls.device, scale.device))
+    lib = load()
+    with torch.no_grad(), torch.cuda.device(cls.device):
+        loc, cls = loc.detach().contiguous(), cls.detach().contiguous()
+        scale = scale.detach().contiguous() if scale is not None else None
+        dev = cls.device
+        points = torch.empty(B, 4, 2, dtype=torch.float32, device=dev)
+        score = torch.empty(B, 4, dtype=torch.float32, device=dev)
+        anchor = torch.empty(B, 4, dtype=torch.int32, device=dev)
+        boxes = torch.empty(B, 4, 4, dtype=torch.int32, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        check(lib.tpg_ssd_landmarks(B, n, C, loc.data_ptr(), cls.data_ptr(), float(conf),
+                                    scale.data_ptr() if scale is not None else None, _LM_PATCH_WH, points.data_ptr(),
+                                    score.data_ptr(), anchor.data_ptr(), boxes.data_ptr(), status.data_ptr(),
+                                    stream_ptr()))
+    return points, score, anchor, boxes, status
+
+
+def u8_to_unit(img_u8, dtype=torch.float32, out=None):
+    """torchvision's ToTensor() on the device (tpg_u8_to_unit): uint8 [N, H, W, C] (HWC) -> u / 255
+    (an IEEE float32 division) as a logical [N, C, H, W] tensor of `dtype` (float32, bfloat16 or
+    float16), channels-last the way the conv kernels take it.  out: a [N, C, H, W] device tensor of
+    any strides to write instead (its dtype is used)."""
+    fn = "u8_to_unit"
+    if not isinstance(img_u8, torch.Tensor) or img_u8.dtype != torch.uint8 or img_u8.dim() != 4:
+        raise ValueError("%s: img_u8 must be a uint8 [N, H, W, C] tensor" % fn)
+    if not img_u8.is_cuda:
+        raise ValueError("%s: img_u8 must be a device tensor, got a %s tensor" % (fn, img_u8.device))
+    n, h, w, c = img_u8.shape
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or tuple(out.shape) != (n, c, h, w) or out.device != img_u8.device:
+            raise ValueError("%s: out must be a [%d, %d, %d, %d] tensor on %s" % (fn, n, c, h, w, img_u8.device))
+        dtype = out.dtype
+    if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError("%s: dtype must be float32, bfloat16 or float16, got %s" % (fn, dtype))
+    if n * h * w >= 1 << 31:
+        raise ValueError("%s: at most 2^31 - 1 pixels, got %d" % (fn, n * h * w))
+    lib = load()
+    with torch.no_grad(), torch.cuda.device(img_u8.device):
+        if out is None:
+            out = new_act(n, c, h, w, dtype, img_u8.device)
+        if out.numel():
+            s = img_u8.stride()
+            strides = (ctypes.c_int64 * 4)(s[0], s[3], s[1], s[2])  # logical (n, c, h, w)
+            check(lib.tpg_u8_to_unit(n, c, h, w, img_u8.data_ptr(), strides, tt(out), stream_ptr()))
+    return out
+
+
+def landmark_accuracy(pred, truth, status=None, thresholds=(5, 10, 18, 30, 45), weights=(1.0, 0.9, 0.65, 0.35, 0.1)):
+    """Pretrain.py's accuracy measure (_calculate_accuracy, :17-64) per image: float32 [B], the mean
+    over the four landmarks of weights[i] where thresholds[i-1] < d <= thresholds[i] (from 0), d the
+    float32 distance between pred and truth (both float32 [B, 4, 2] or [B, 8]).  As the reference,
+    an exact hit (d == 0) scores 0; so do a NaN distance and a landmark whose missing bit is set in
+    status (int32 [B], ssd_landmarks's)."""
+    fn = "landmark_accuracy"
+    ok = lambda t: t.dtype == torch.float32 and t.dim() in (2, 3) and t.numel() == t.shape[0] * 8  # noqa: E731
+    _lm_arg(fn, "pred", pred, "[B, 4, 2]", ok)
+    _lm_arg(fn, "truth", truth, "[B, 4, 2]", ok)
+    B = pred.shape[0]
+    if truth.shape[0] != B or truth.device != pred.device or B < 1:
+        raise ValueError("%s: pred %s on %s and truth %s on %s must match and hold a face" %
+                         (fn, tuple(pred.shape), pred.device, tuple(truth.shape), truth.device))
+    if status is not None:
+        if not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or tuple(status.shape) != (B,):
+            raise ValueError("%s: status must be an int32 [%d] tensor" % (fn, B))
+        if status.device != pred.device:
+            raise ValueError("%s: status must be on %s, got %s" % (fn, pred.device, status.device))
+    thresholds, weights = [float(v) for v in thresholds], [float(v) for v in weights]
+    nb = len(thresholds)
+    if not 1 <= nb <= LM_MAX_BANDS or len(weights) != nb:
+        raise ValueError("%s: 1..%d bands with one weight each, got %d thresholds and %d weights" %
+                         (fn, LM_MAX_BANDS, nb, len(weights)))
+    if any(not b >= a for a, b in zip([0.0] + thresholds, thresholds)):
+        raise ValueError("%s: thresholds must ascend from 0, got %s" % (fn, thresholds))
+    lib = load()
+    with torch.no_grad(), torch.cuda.device(pred.device):
+        pred, truth = pred.detach().contiguous(), truth.detach().contiguous()
+        status = status.contiguous() if status is not None else None
+        acc = torch.empty(B, dtype=torch.float32, device=pred.device)
+        check(lib.tpg_landmark_accuracy(B, pred.data_ptr(), truth.data_ptr(),
+                                        status.data_ptr() if status is not None else None, nb,
+                                        (ctypes.c_float * nb)(*thresholds), (ctypes.c_float * nb)(*weights),
+                                        acc.data_ptr(), stream_ptr()))
+    return acc
 
 
 # ---- inference image path (tpg_image.hip): [-1, 1] activations -> u8 HWC pixels, and the
