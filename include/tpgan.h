@@ -33,6 +33,11 @@
  *   tpg_resize_u8           Image.resize(size, Image.LANCZOS) of RGB u8 images of different sizes,
  *                           bit for bit (DataAndDataset.py:247-251); tpg_resize_coeffs and
  *                           tpg_resize_pack_job build its tables and job records on the host
+ *   tpg_similarity_fit      least-squares similarity transform from a template of face points to each
+ *                           face's detected points, and tpg_affine_warp_u8, the photo resampled
+ *                           through it into the generator's frame (build-defined, no reference code:
+ *                           the reference's TestDataset only takes tight, upright face crops);
+ *                           tpg_warp_pack_job builds the warp's job records on the host
  *   tpg_denorm_u8           the generator's [-1, 1] output back to u8 HWC pixels: ToPILImage /
  *                           torchvision.utils.save_image's rounding of (x+1)/2 (the reference has no
  *                           inference script; its training loop would save samples that way)
@@ -546,6 +551,71 @@ int32_t tpg_resize_pack_job(void* jobs, int32_t index, const uint8_t* src, int32
                             int64_t ws_off);
 int32_t tpg_resize_u8(int32_t njobs, const void* jobs_dev, const int32_t* tables_dev, int32_t out_h, int32_t out_w,
                       uint8_t* out, void* ws, tpg_stream_t stream);
+
+/* Face alignment: the step between the landmark detector and the generator.  Fit the similarity
+ * transform from a template of K points in the OUTPUT frame onto each face's K points in PHOTO
+ * pixels (output frame -> photo: the direction the warp samples in, nothing is inverted), then
+ * resample every photo through its matrix.  Two launches for B faces, no host round trip: the warp
+ * reads the fit's 16.16 matrices from device memory.
+ *
+ *   tpg_similarity_fit     points: device float [B][K][2] (x, y); tmpl: HOST float [K][2], the same
+ *                          for every face; 2 <= K <= 8.  Per face, in float32 with IEEE divisions,
+ *                          sums over the points in index order and no FMA contraction:
+ *                            qm = sum(q) / K, qc = q - qm, S = sum(qc.x*qc.x + qc.y*qc.y)  (host)
+ *                            pm = sum(p) / K, pc = p - pm
+ *                            a = sum(qc.x*pc.x + qc.y*pc.y) / S
+ *                            b = sum(qc.x*pc.y - qc.y*pc.x) / S
+ *                            tx = pm.x - (a*qm.x - b*qm.y),  ty = pm.y - (b*qm.x + a*qm.y)
+ *                          matrix: float [B][6] = (a, -b, tx, b, a, ty), photo = M * out + t;
+ *                          matrix_q16: int32 [B][6], each entry rint(v * 65536.0f) (ties to even);
+ *                          status: int32 [B]:
+ *                            bit 0 (1)  a coordinate of p is NaN, infinite or |v| > 1e9
+ *                            bit 1 (2)  degenerate or out of range: a*a + b*b is zero or not finite,
+ *                                       sqrt(a*a + b*b) > 32, or |tx| >= 16384 or |ty| >= 16384
+ *                                       (tested only where bit 0 is clear)
+ *                            bit 2 (4)  in_status[face] != 0 (in_status: device int32 [B] or NULL;
+ *                                       tpg_ssd_landmarks's status, so "not found" travels on)
+ *                          A face with bit 0 or bit 1 gets the identity (1, 0, 0, 0, 1, 0); every
+ *                          slot of the three outputs is written on every call.  The template is
+ *                          checked on the host before any device work: finite, with S > 0 and finite.
+ *   tpg_warp_job_bytes     size of one job record (32)
+ *   tpg_warp_pack_job      write record `index` of the HOST array `jobs`; the caller uploads it.
+ *                          Record layout (little endian, 32 bytes):
+ *                            0 src pointer (device, RGB u8 HWC)   8 row stride in bytes (>= W*3)
+ *                            16 H  20 W  24 out_h  28 out_w  (int32)
+ *                          Sides are 1..4096; bands must be 3.
+ *   tpg_affine_warp_u8     out: u8 [njobs][out_h][out_w][3]; matrix_q16: device int32 [njobs][6] =
+ *                          (m00, m01, tx, m10, m11, ty) in 16.16 fixed point, ANY affine map, not
+ *                          only a similarity; status: device int32 [njobs].  njobs <= 65535.  Integer
+ *                          arithmetic only on the device.  Per photo:
+ *                            d = max(m00^2 + m10^2, m01^2 + m11^2), exact (it can reach 2^63)
+ *                            n = the smallest integer in 1..16 with (n * 65536)^2 >= d; if there is
+ *                                none, n = 16 and status bit 3 (8) is set: a warning, the output
+ *                                is written all the same, undersampled.  Otherwise status is 0.
+ *                          Per output pixel (ox, oy) and sub-sample (i, j), i, j in 0..n-1, in int64:
+ *                            U = 2n*ox + 2i + 1,  V = 2n*oy + 2j + 1
+ *                            X = tx + floor((m00*U + m01*V) / 2n) - 32768
+ *                            Y = ty + floor((m10*U + m11*V) / 2n) - 32768
+ *                          (pixel centres: output pixel ox covers [ox, ox + 1), source pixel ix has
+ *                          its centre at ix + 0.5, hence the -32768).  Bilinear taps:
+ *                            ix = X >> 16 (arithmetic), fx = (X >> 8) & 255; iy, fy likewise
+ *                            columns ix, ix + 1 clamped to [0, W-1], rows iy, iy + 1 to [0, H-1]
+ *                            weights (256 - fx, fx) x (256 - fy, fy), summing to 65536
+ *                          Per channel acc = sum over sub-samples and taps of weight * pixel, and
+ *                            out = (acc + 32768*n*n) / (65536*n*n)     (round half up)
+ *                          So the identity matrix copies the top-left out_h x out_w of the photo
+ *                          (edge-replicated beyond it), (131072, 0, 0, 0, 131072, 0) is the
+ *                          round-half-up 2 x 2 box average and (0, -65536, W*65536, 65536, 0, 0) a
+ *                          quarter turn.  One block per 16 x 16 output tile of one photo.  A record
+ *                          built for another (out_h, out_w) is skipped: nothing of that photo is
+ *                          read, and neither its slot of out nor its status word is written. */
+int32_t tpg_similarity_fit(int32_t B, int32_t K, const float* points, const float* tmpl, const int32_t* in_status,
+                           float* matrix, int32_t* matrix_q16, int32_t* status, tpg_stream_t stream);
+size_t tpg_warp_job_bytes(void);
+int32_t tpg_warp_pack_job(void* jobs, int32_t index, const uint8_t* src, int32_t h, int32_t w, int32_t bands,
+                          int64_t row_stride, int32_t out_h, int32_t out_w);
+int32_t tpg_affine_warp_u8(int32_t njobs, const void* jobs_dev, const int32_t* matrix_q16, int32_t out_h,
+                           int32_t out_w, uint8_t* out, int32_t* status, tpg_stream_t stream);
 
 /* Inference image path.
  *   tpg_denorm_u8  x: logical [n, c, h, w], TPG_F32 / TPG_BF16 / TPG_F16, any element strides (the

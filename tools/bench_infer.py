@@ -36,6 +36,18 @@ B = 32 synthetic raw photos, after warm-up, HIP events and the host clock around
     baseline the route there was before it on the same tensors: MultiTaskDecoder()(loc, cls), the
     lists assembled into a host array, uploaded, FaceBatcher.landmark_boxes.
 
+--align runs the face-alignment leg instead (profiles/r12/align.txt), in one process, bf16, B = 32
+synthetic raw photos of four different sizes, after warm-up, HIP events and the host clock, the
+median of `rounds` interleaved rounds with the spread:
+
+  - LandmarkDetector.detect(imgs) and LandmarkDetector.detect(imgs, aligner=...): the front end with
+    one pass and with fit + warp + a second pass (an untrained detector: the points are wherever
+    its best anchors are, the work per call is that of a trained one);
+  - FaceAligner.align alone on planted points (the template under a tilt of up to 20 degrees, the
+    face 45 % of the photo's width), then tpgan_ops.similarity_fit and tpgan_ops.affine_warp_u8
+    alone as back-to-back calls, with the sub-sampling factors the matrices gave.
+  --commit names the tree the numbers are from; the first line records it and the device.
+
 Prints one JSON line per measurement; --out also writes them to a file.
 """
 import argparse
@@ -200,6 +212,125 @@ def detect_leg(a, emit):
     emit(line)
 
 
+ALIGN_TEMPLATE = [[44.0, 52.0], [84.0, 52.0], [64.0, 76.0], [64.0, 98.0]]  # a plausible frame, not a measured one
+
+
+def align_leg(a, emit):
+    import MobileNetV2 as MN
+    import tpgan_infer
+    import tpgan_ops
+    dev = torch.device("cuda", 0)
+    B = a.batch
+    sizes = [(480, 640), (640, 480), (768, 1024), (300, 250)]  # (H, W), cycled over the batch
+    rng = np.random.default_rng(0)
+    hw = [sizes[i % len(sizes)] for i in range(B)]
+    imgs = [torch.from_numpy(rng.integers(0, 256, (h, w, 3), dtype=np.uint8)).to(dev) for h, w in hw]
+    emit({"device": torch.cuda.get_device_name(0), "hip": torch.version.hip, "commit": a.commit, "batch": B,
+          "photo_sizes_hw": sizes, "compute_dtype": "bf16"})
+    torch.manual_seed(0)
+    det = tpgan_infer.LandmarkDetector(MN.MobileNetV2(), device=dev, compute_dtype=torch.bfloat16, max_batch=B,
+                                       on_missing="best")
+    al = tpgan_infer.FaceAligner(ALIGN_TEMPLATE, device=dev)
+    iters, kiters = max(a.iters, 100), max(a.kiters, 2000)
+
+    def rounds(fns, n):
+        """Interleaved rounds of the given calls -> per call (median events ms, median host ms, [min, max])."""
+        t = [[] for _ in fns]
+        for _ in range(a.rounds):
+            for k, fn in enumerate(fns):
+                t[k].append(events(fn, n))
+        return [(float(np.median([x[0] for x in r])), float(np.median([x[1] for x in r])),
+                 [round(min(x[0] for x in r), 4), round(max(x[0] for x in r), 4)]) for r in t]
+
+    # planted points: the template's 128 x 128 frame scaled to 45 % of the photo's width, tilted
+    q = np.asarray(ALIGN_TEMPLATE, np.float64)
+    pts = []
+    for h, w in hw:
+        s, th = 0.45 * w / 128.0, np.deg2rad(rng.uniform(-20, 20))
+        r = np.array([[np.cos(th), -np.sin(th)], [np.sin(th), np.cos(th)]])
+        pts.append(s * (q - q.mean(0)) @ r.T + [0.5 * w, 0.45 * h])
+    pts = torch.from_numpy(np.stack(pts).astype(np.float32)).to(dev)
+    for _ in range(5):
+        res = al.align(imgs, pts)
+    torch.cuda.synchronize()
+    assert res["status"].tolist() == [0] * B
+    mq = res["matrix_q16"]
+    n_of = []
+    for m in mq.reshape(B, 6).tolist():
+        d = max(m[0] * m[0] + m[3] * m[3], m[1] * m[1] + m[4] * m[4])
+        n_of.append(next(n for n in range(1, 17) if (n * 65536) ** 2 >= d))
+    (ms_a, wall_a, mm_a), (ms_f, wall_f, mm_f), (ms_w, wall_w, mm_w) = rounds(
+        [lambda: al.align(imgs, pts), lambda: tpgan_ops.similarity_fit(pts, al.template),
+         lambda: tpgan_ops.affine_warp_u8(imgs, mq)], kiters)
+    out_bytes = B * 128 * 128 * 3
+    taps = sum(n * n for n in n_of) * 128 * 128 * 4
+    emit({"op": "FaceAligner.align (fit + warp, mixed-size photos -> u8 128x128x3), planted points", "batch": B,
+          "rounds": a.rounds, "calls_per_round": kiters, "us_per_call": round(ms_a * 1e3, 2),
+          "us_per_call_min_max": [round(v * 1e3, 2) for v in mm_a], "us_per_call_host_clock": round(wall_a * 1e3, 2),
+          "faces_per_s": round(B / (ms_a * 1e-3), 1), "subsampling_n_per_photo": sorted(set(n_of)),
+          "device_to_host_copies": 0})
+    emit({"op": "tpg_similarity_fit alone, back-to-back calls", "batch": B, "calls_per_round": kiters,
+          "us_per_call": round(ms_f * 1e3, 2), "us_per_call_min_max": [round(v * 1e3, 2) for v in mm_f],
+          "us_per_call_host_clock": round(wall_f * 1e3, 2)})
+    emit({"op": "tpg_affine_warp_u8 alone (job table upload + one launch), back-to-back calls", "batch": B,
+          "calls_per_round": kiters, "us_per_call": round(ms_w * 1e3, 2),
+          "us_per_call_min_max": [round(v * 1e3, 2) for v in mm_w], "us_per_call_host_clock": round(wall_w * 1e3, 2),
+          "out_bytes": out_bytes, "bilinear_taps": taps, "Gtaps_per_s": round(taps / (ms_w * 1e-3) / 1e9, 1),
+          "note": "events span the host's record packing and upload too: at this size the call is bound by them "
+                  "when the host clock equals the event time"})
+
+    # the warp kernel alone: the job table resident, the output reused, the C entry point called directly
+    import ctypes
+    import tpgan_lib as L
+    lib = L.load()
+    jb = lib.tpg_warp_job_bytes()
+    jobs = (ctypes.c_uint8 * (B * jb))()
+    for i, t in enumerate(imgs):
+        L.check(lib.tpg_warp_pack_job(jobs, i, t.data_ptr(), t.shape[0], t.shape[1], 3, t.stride(0), 128, 128))
+    jobs_dev = torch.frombuffer(jobs, dtype=torch.uint8).to(dev)
+    out = torch.empty(B, 128, 128, 3, dtype=torch.uint8, device=dev)
+    wst = torch.empty(B, dtype=torch.int32, device=dev)
+    args = (B, jobs_dev.data_ptr(), mq.data_ptr(), 128, 128, out.data_ptr(), wst.data_ptr(), L.stream_ptr())
+
+    def kernel():
+        lib.tpg_affine_warp_u8(*args)
+    for _ in range(5):
+        kernel()
+    torch.cuda.synchronize()
+    assert torch.equal(out, res["u8"])
+    (ms_k, wall_k, mm_k), = rounds([kernel], kiters)
+    emit({"op": "affine_warp_kernel alone (resident job table, C entry point, back-to-back launches)", "batch": B,
+          "calls_per_round": kiters, "us_per_launch": round(ms_k * 1e3, 2),
+          "us_per_launch_min_max": [round(v * 1e3, 2) for v in mm_k], "us_per_launch_host_clock": round(wall_k * 1e3, 2),
+          "blocks": 64 * B, "bilinear_taps": taps, "Gtaps_per_s": round(taps / (ms_k * 1e-3) / 1e9, 1),
+          "note": "an upper bound of the kernel time: launches queue back to back, so when the host clock equals "
+                  "the event time this too is the host's launch rate"})
+
+    # the front end with one pass and with two
+    for _ in range(3):
+        det.detect(imgs)
+    try:
+        for _ in range(3):
+            d = det.detect(imgs, aligner=al)
+    except ValueError as e:  # the untrained detector put a face's four points on one spot: no timing to report
+        emit({"op": "LandmarkDetector.detect with the aligner", "error": str(e)})
+        (ms, wall, mm), = rounds([lambda: det.detect(imgs)], iters)
+        emit({"op": "LandmarkDetector.detect (mixed-size photos -> points, boxes, status), bf16", "batch": B,
+              "rounds": a.rounds, "calls_per_round": iters, "ms_per_batch": round(ms, 3), "ms_per_batch_min_max": mm,
+              "ms_per_batch_host_clock": round(wall, 3)})
+        return
+    torch.cuda.synchronize()
+    (ms, wall, mm), (ms2, wall2, mm2) = rounds([lambda: det.detect(imgs), lambda: det.detect(imgs, aligner=al)], iters)
+    emit({"op": "LandmarkDetector.detect (mixed-size photos -> points, boxes, status), bf16", "batch": B,
+          "rounds": a.rounds, "calls_per_round": iters, "ms_per_batch": round(ms, 3), "ms_per_batch_min_max": mm,
+          "ms_per_batch_host_clock": round(wall, 3), "faces_per_s": round(B / (ms * 1e-3), 1)})
+    emit({"op": "LandmarkDetector.detect(imgs, aligner) (detect, fit, warp, detect again), bf16", "batch": B,
+          "rounds": a.rounds, "calls_per_round": iters, "ms_per_batch": round(ms2, 3), "ms_per_batch_min_max": mm2,
+          "ms_per_batch_host_clock": round(wall2, 3), "faces_per_s": round(B / (ms2 * 1e-3), 1),
+          "over_one_pass": round(ms2 / ms, 3), "align_status_or": int(d["align_status"].max()),
+          "note": "ends with the one read of the three status arrays"})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -210,17 +341,19 @@ def main():
     ap.add_argument("--identity", action="store_true", help="the identity-scoring leg instead of the image path")
     ap.add_argument("--rounds", type=int, default=5, help="interleaved rounds of the identity leg")
     ap.add_argument("--detect", action="store_true", help="the landmark-detector leg instead of the image path")
+    ap.add_argument("--align", action="store_true", help="the face-alignment leg instead of the image path")
+    ap.add_argument("--commit", default="unknown", help="the tree the numbers are from (recorded by --align)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_infer.py needs a ROCm GPU (there is no CPU path)")
-    if a.identity or a.detect:
+    if a.identity or a.detect or a.align:
         lines = []
 
         def emit_id(d):
             lines.append(json.dumps(d))
             print(lines[-1], flush=True)
-        (identity_leg if a.identity else detect_leg)(a, emit_id)
+        (identity_leg if a.identity else detect_leg if a.detect else align_leg)(a, emit_id)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:

@@ -27,6 +27,10 @@
 // The landmark front end's entry points (tpg_ssd_landmarks, tpg_landmark_accuracy, tpg_u8_to_unit)
 // likewise: NULL pointers and sizes outside their ranges (n = 0 and 4097, C = 4, 0 and 9 bands, ...),
 // with the host-read tables (patch sizes, band edges and weights, strides) in exact-size heap blocks.
+// The face alignment's host side (tpg_align.hip) too: tpg_warp_pack_job into a heap block of exactly
+// two records, tpg_similarity_fit's template check with the template in an exact-size heap block of
+// K * 2 floats (non-finite, coincident and overflowing templates, K outside 2..8), and every argument
+// tpg_similarity_fit and tpg_affine_warp_u8 reject, which must stop them before any device work.
 // Built with `make -C tp-gan_amd asan` (the host-logic units compiled with -fsanitize=address on
 // the host side only; the kernels are the product's) and run by tests/test_capi.py.
 // Exit status: 0 clean, 1 a consistency check failed; ASan aborts on a memory error.
@@ -308,6 +312,69 @@ static void resize_jobs() {
   accepted += tpg_resize_u8(-1, jobs, (const int32_t*)jobs, 128, 128, (uint8_t*)jobs, nullptr, nullptr) == 0;
   if (accepted) { fprintf(stderr, "resize: %d malformed calls accepted\n", accepted); g_fail = 1; }
   free(jobs);
+}
+
+// Face alignment: the job builder and the two launch entry points' validation.  Every launch call is
+// malformed in exactly one way; device pointers are fake and never dereferenced on the host.
+static void align_sweep() {
+  const size_t jb = tpg_warp_job_bytes();
+  char* jobs = (char*)malloc(jb * 2);  // records 0 and 1, nothing after them
+  const uint8_t* src = (const uint8_t*)0x10000;
+  void* devp = (void*)0x20000;
+  const int bad[] = {0, -1, 4097, -2147483647 - 1, 2147483647};
+  if (jb != 32 || tpg_warp_pack_job(jobs, 0, src, 480, 640, 3, 1920, 128, 128) != 0 ||
+      tpg_warp_pack_job(jobs, 1, src, 4096, 4096, 3, 12288 + 64, 1, 4096) != 0) {
+    fprintf(stderr, "warp job builder rejected a valid job: %s\n", tpg_last_error());
+    g_fail = 1;
+  }
+  int accepted = 0;
+  for (int v : bad) {
+    accepted += tpg_warp_pack_job(jobs, 1, src, v, 640, 3, 1920, 128, 128) == 0;
+    accepted += tpg_warp_pack_job(jobs, 1, src, 480, v, 3, 12288, 128, 128) == 0;
+    accepted += tpg_warp_pack_job(jobs, 1, src, 480, 640, 3, 1920, v, 128) == 0;
+    accepted += tpg_warp_pack_job(jobs, 1, src, 480, 640, 3, 1920, 128, v) == 0;
+    accepted += tpg_warp_pack_job(jobs, 1, src, 480, 640, v, 1920, 128, 128) == 0;
+    accepted += tpg_warp_pack_job(jobs, 1, src, 480, 640, 3, v < 1920 ? v : 1919, 128, 128) == 0;
+    accepted += tpg_affine_warp_u8(1, devp, (const int32_t*)devp, v, 128, (uint8_t*)devp, (int32_t*)devp, nullptr) == 0;
+    accepted += tpg_affine_warp_u8(1, devp, (const int32_t*)devp, 128, v, (uint8_t*)devp, (int32_t*)devp, nullptr) == 0;
+  }
+  accepted += tpg_warp_pack_job(jobs, -1, src, 480, 640, 3, 1920, 128, 128) == 0;
+  accepted += tpg_warp_pack_job(jobs, 1, nullptr, 480, 640, 3, 1920, 128, 128) == 0;
+  accepted += tpg_warp_pack_job(nullptr, 1, src, 480, 640, 3, 1920, 128, 128) == 0;
+  accepted += tpg_affine_warp_u8(-1, devp, (const int32_t*)devp, 128, 128, (uint8_t*)devp, (int32_t*)devp, nullptr) == 0;
+  accepted += tpg_affine_warp_u8(65536, devp, (const int32_t*)devp, 128, 128, (uint8_t*)devp, (int32_t*)devp, nullptr) == 0;
+  accepted += tpg_affine_warp_u8(1, nullptr, (const int32_t*)devp, 128, 128, (uint8_t*)devp, (int32_t*)devp, nullptr) == 0;
+  accepted += tpg_affine_warp_u8(1, devp, nullptr, 128, 128, (uint8_t*)devp, (int32_t*)devp, nullptr) == 0;
+  accepted += tpg_affine_warp_u8(1, devp, (const int32_t*)devp, 128, 128, nullptr, (int32_t*)devp, nullptr) == 0;
+  accepted += tpg_affine_warp_u8(1, devp, (const int32_t*)devp, 128, 128, (uint8_t*)devp, nullptr, nullptr) == 0;
+  free(jobs);
+  float* fd = (float*)devp;
+  int32_t* id = (int32_t*)devp;
+  for (int K = 2; K <= 8; ++K) {
+    float* t = (float*)malloc(sizeof(float) * 2 * K);  // exactly K points: the check reads no further
+    for (int k = 0; k < 2 * K; ++k) t[k] = 7.0f;       // coincident
+    accepted += tpg_similarity_fit(4, K, fd, t, nullptr, fd, id, id, nullptr) == 0;
+    for (int k = 0; k < 2 * K; ++k) t[k] = (float)(k * k % 11);
+    t[2 * K - 1] = __builtin_nanf("");
+    accepted += tpg_similarity_fit(4, K, fd, t, nullptr, fd, id, id, nullptr) == 0;
+    t[2 * K - 1] = __builtin_inff();
+    accepted += tpg_similarity_fit(4, K, fd, t, nullptr, fd, id, id, nullptr) == 0;
+    t[2 * K - 1] = 3.0e38f;
+    t[0] = -3.0e38f;  // finite points whose spread overflows float32
+    accepted += tpg_similarity_fit(4, K, fd, t, nullptr, fd, id, id, nullptr) == 0;
+    t[2 * K - 1] = 5.0f;
+    t[0] = 1.0f;  // a good template: each missing pointer alone
+    accepted += tpg_similarity_fit(4, K, nullptr, t, nullptr, fd, id, id, nullptr) == 0;
+    accepted += tpg_similarity_fit(4, K, fd, t, nullptr, nullptr, id, id, nullptr) == 0;
+    accepted += tpg_similarity_fit(4, K, fd, t, nullptr, fd, nullptr, id, nullptr) == 0;
+    accepted += tpg_similarity_fit(4, K, fd, t, nullptr, fd, id, nullptr, nullptr) == 0;
+    accepted += tpg_similarity_fit(-1, K, fd, t, nullptr, fd, id, id, nullptr) == 0;
+    free(t);
+  }
+  float two[4] = {0, 0, 1, 1};
+  for (int K : {-1, 0, 1, 9, 2147483647}) accepted += tpg_similarity_fit(4, K, fd, two, nullptr, fd, id, id, nullptr) == 0;
+  accepted += tpg_similarity_fit(4, 2, fd, nullptr, nullptr, fd, id, id, nullptr) == 0;
+  if (accepted) { fprintf(stderr, "align: %d malformed calls accepted\n", accepted); g_fail = 1; }
 }
 
 // Identity search: the chunk planner and the validation of tpg_l2_normalize / tpg_cosine_topk /
@@ -608,6 +675,7 @@ int main(int argc, char** argv) {
   resize_jobs();
   identity_sweep(iters < 2000 ? iters : 2000);
   landmark_sweep();
+  align_sweep();
   printf("planner_asan: %ld valid, %ld rejected descriptors, %ld pack jobs, %ld wgrad plans, %ld data plans, "
          "%ld resize tables, %ld top-k plans, %s\n", g_valid, g_rejected, g_jobs, g_plans, g_dplans, g_tables, g_idplans,
          g_fail ? "FAILED" : "ok");

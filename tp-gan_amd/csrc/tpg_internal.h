@@ -595,6 +595,13 @@ int launch_landmark_accuracy(int B, const float* pred, const float* truth, const
                              const float* thresholds, const float* weights, float* acc, hipStream_t s);
 int launch_u8_to_unit(int n, int c, int h, int w, const uint8_t* img, const int64_t* img_stride, const tpg_tensor& out,
                       hipStream_t s);
+// face alignment (tpg_align.hip): similarity fit of K template points (HOST float [K][2], finite) onto
+// each face's points, -1 before any launch when the template points coincide; the affine warp of
+// njobs photos (device WarpJob records and 16.16 matrices) into u8 [njobs][out_h][out_w][3]
+int launch_similarity_fit(int B, int K, const float* tmpl, const float* points, const int* in_status, float* matrix,
+                          int* matrix_q16, int* status, hipStream_t s);
+int launch_affine_warp_u8(int njobs, const void* jobs_dev, const int* matrix_q16, int out_h, int out_w, uint8_t* out,
+                          int* status, hipStream_t s);
 int launch_pack_halo(const PackArgs& a, int nks, int bn, int ntiles, hipStream_t s);
 // elementwise launchers behind the C entry points of the same names (tpg_elementwise.hip);
 // launch_adam / launch_grad_check: -1 for misaligned buffers, before any launch

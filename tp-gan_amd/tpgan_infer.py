@@ -13,6 +13,9 @@ uint8 frontal faces, and PSNR / SSIM against the ground-truth frontal view.
     fz = Frontalizer(G, detector=det)
     u8 = fz(imgs)                                            # no landmarks supplied
     d = det.detect(imgs)                                     # points, score, boxes, status, ...
+    al = FaceAligner(FaceAligner.template_from_landmarks(train_lm68, train_scale))
+    fz = Frontalizer(G, detector=det, aligner=al)            # small, off-centre or tilted faces
+    d = det.detect(imgs, aligner=al)                         # ... of the aligned faces, + matrix
 
 The data path is FaceBatcher.from_raw (Pillow-exact LANCZOS, landmark crops, [-1, 1]), the
 model is the product's Generator frozen in eval mode, the way back to pixels is
@@ -29,6 +32,13 @@ Without landmarks, LandmarkDetector finds the four crop centres itself: LANCZOS 
 tpgan_ops.u8_to_unit ([0, 1], what the detector was trained on), the MobileNetV2 + SSD head, and
 tpgan_ops.ssd_landmarks, which decodes the head's outputs straight into FaceBatcher.from_points'
 crop boxes.  One status word per face is the only thing read back.
+
+The detector alone sees the whole photo squashed to 128 x 128, which is the generator's frame only
+for a tight, upright face crop.  FaceAligner closes the gap: tpgan_ops.similarity_fit fits the
+rotation + scale + translation from a template of the four points onto the detected ones, and
+tpgan_ops.affine_warp_u8 resamples the photo through it (integer bilinear, sub-sampled where the
+map shrinks); the detector then runs a second time on the aligned faces, whose points and boxes
+are what the generator's crops use.
 """
 import os
 import re
@@ -73,6 +83,7 @@ def _photo_wh(imgs):
 
 
 _NAN_POINT = "cannot convert float NaN to integer: a landmark point of face(s) %s is NaN or infinite"
+_BAD_ALIGN = "cannot align face(s) %s: %s"
 
 
 class Frontalizer:
@@ -86,9 +97,12 @@ class Frontalizer:
     max_batch       faces per forward pass of __call__ / frontalize_batch.
     detector        a LandmarkDetector on the same device, or None.  With one, __call__ and evaluate
                     take lm68=None: the detector's four points are the crop centres.
+    aligner         a FaceAligner on the same device (128 x 128 output), or None; needs a detector.
+                    With one, photos without landmarks are first warped into the template's frame
+                    (LandmarkDetector.detect(imgs, aligner=...)); calls that give lm68 are unchanged.
     """
 
-    def __init__(self, G, device="cuda", compute_dtype=torch.bfloat16, max_batch=32, detector=None):
+    def __init__(self, G, device="cuda", compute_dtype=torch.bfloat16, max_batch=32, detector=None, aligner=None):
         if compute_dtype not in (torch.float32, torch.bfloat16, torch.float16):
             raise ValueError("compute_dtype must be float32, bfloat16 or float16, got %s" % compute_dtype)
         if int(max_batch) < 1:
@@ -104,6 +118,16 @@ class Frontalizer:
             if detector.device != self.device:
                 raise ValueError("detector is on %s, the Frontalizer on %s" % (detector.device, self.device))
         self.detector = detector
+        if aligner is not None:
+            if not isinstance(aligner, FaceAligner):
+                raise ValueError("aligner must be a FaceAligner or None, got %s" % type(aligner).__name__)
+            if detector is None:
+                raise ValueError("an aligner needs a detector: its points are what the faces are aligned by")
+            if aligner.device != self.device:
+                raise ValueError("aligner is on %s, the Frontalizer on %s" % (aligner.device, self.device))
+            if aligner.out_hw != (128, 128):
+                raise ValueError("the generator's frame is 128 x 128, the aligner's %s" % (aligner.out_hw,))
+        self.aligner = aligner
         self.G = G
         self.zdim = G.global_pathway.zdim
         self.img_size = G.img_size
@@ -218,7 +242,7 @@ class Frontalizer:
             if B == 0:
                 return out
             # every face's landmarks first: nothing is returned for a batch with a bad one
-            d = self.detector.detect(imgs)
+            d = self.detector.detect(imgs) if self.aligner is None else self.detector.detect(imgs, aligner=self.aligner)
             fb = self._batcher()
             for s in range(0, B, self.max_batch):
                 e = min(B, s + self.max_batch)
@@ -247,7 +271,8 @@ class Frontalizer:
 
     def evaluate(self, imgs, lm68, frontal, z=None, identity=None):
         """Frontalise and score against the ground-truth frontal view (uint8 [B, 128, 128, 3] on the
-        device, or a list of raw photos, resized like the inputs) -> {"fake_u8", "sse" int64 [B],
+        device, or a list of raw photos, resized like the inputs; with an aligner and lm68=None they
+        are aligned like the inputs, by the detector's points on them) -> {"fake_u8", "sse" int64 [B],
         "psnr" float64 [B] (inf where sse is 0), "ssim" float32 [B]}.  lm68 as __call__.  With identity=an
         IdentityScorer the dict also holds "id_cos" float32 [B]: the cosine similarity of the
         identity embeddings of the frontalised face and of the true frontal view."""
@@ -258,6 +283,8 @@ class Frontalizer:
             if frontal.dtype != torch.uint8:
                 raise ValueError("frontal must be uint8 [B, 128, 128, 3] or a list of raw photos")
             real = frontal.to(self.device).contiguous()
+        elif self.aligner is not None and lm68 is None:
+            real = self.detector.detect(self._u8_images(frontal, "frontal"), aligner=self.aligner)["u8_128"]
         else:
             real = self._batcher().resize(self._u8_images(frontal, "frontal"), (128, 128))
         if real.shape != fake.shape:
@@ -520,36 +547,24 @@ class LandmarkDetector:
             loc, cls = self.model(tpgan_ops.u8_to_unit(u8, self.compute_dtype))
         return loc.float(), cls.float()
 
-    def detect(self, imgs):
-        """imgs: uint8 photos, a list of [H_i, W_i, 3] (any mix of sizes) or one [B, H, W, 3] ->
-        {"points" float32 [B, 4, 2] (x, y) of the left eye, right eye, nose and mouth centre in the
-        128 x 128 frame, "points_photo" the same in each photo's own pixels (times float32 (W / 128,
-        H / 128)), "score" float32 [B, 4], "anchor" int32 [B, 4], "boxes" int32 [B, 4, 4] (left, upper,
-        right, lower: FaceBatcher.from_points takes them), "status" int32 [B] (tpgan_ops.ssd_landmarks),
-        "u8_128" uint8 [B, 128, 128, 3]}.  The status read is the call's only copy to the host."""
-        imgs = _u8_images(self.device, imgs, "imgs")
-        B = len(imgs)
-        if B == 0:
-            raise ValueError("imgs holds no photos")
-        fb = self._batcher()
+    def _decode(self, u8_128):
+        """One detector pass over uint8 [B, 128, 128, 3] faces: tpgan_ops.ssd_landmarks's tuple."""
+        B = u8_128.shape[0]
         dh, dw = self.detect_hw
-        with torch.no_grad(), torch.cuda.device(self.device):
-            u8_128 = fb.resize(imgs, (128, 128))
-            u8_det = u8_128 if (dh, dw) == (128, 128) else fb.resize(u8_128, (dh, dw))
-            heads = [self._head(u8_det[s:s + self.max_batch]) for s in range(0, B, self.max_batch)]
-            loc = heads[0][0] if len(heads) == 1 else torch.cat([h[0] for h in heads])
-            cls = heads[0][1] if len(heads) == 1 else torch.cat([h[1] for h in heads])
-            if loc.shape[1] > 4096:
-                raise ValueError("detect_hw %s gives %d anchors; the decode takes at most 4096" %
-                                 (self.detect_hw, loc.shape[1]))
-            scale = None
-            if (dh, dw) != (128, 128):
-                one = (128.0 / np.array([dw, dh], np.float64)).astype(np.float32)
-                scale = torch.from_numpy(np.tile(one, (B, 1))).to(self.device)
-            points, score, anchor, boxes, status = tpgan_ops.ssd_landmarks(loc, cls, self.confidence_threshold, scale)
-            to_photo = torch.from_numpy((_photo_wh(imgs) / 128.0).astype(np.float32)).to(self.device)
-            points_photo = points * to_photo[:, None, :]
-            st = status.tolist()  # the one device-to-host copy
+        u8_det = u8_128 if (dh, dw) == (128, 128) else self._batcher().resize(u8_128, (dh, dw))
+        heads = [self._head(u8_det[s:s + self.max_batch]) for s in range(0, B, self.max_batch)]
+        loc = heads[0][0] if len(heads) == 1 else torch.cat([h[0] for h in heads])
+        cls = heads[0][1] if len(heads) == 1 else torch.cat([h[1] for h in heads])
+        if loc.shape[1] > 4096:
+            raise ValueError("detect_hw %s gives %d anchors; the decode takes at most 4096" %
+                             (self.detect_hw, loc.shape[1]))
+        scale = None
+        if (dh, dw) != (128, 128):
+            one = (128.0 / np.array([dw, dh], np.float64)).astype(np.float32)
+            scale = torch.from_numpy(np.tile(one, (B, 1))).to(self.device)
+        return tpgan_ops.ssd_landmarks(loc, cls, self.confidence_threshold, scale)
+
+    def _check_status(self, st):
         bad = [i for i, v in enumerate(st) if v & 16]
         if bad:
             raise ValueError(_NAN_POINT % bad)
@@ -559,9 +574,161 @@ class LandmarkDetector:
                 raise ValueError("no anchor above confidence %g for face(s) %s: %s" %
                                  (self.confidence_threshold, sorted(missing),
                                   ", ".join("%d: %s" % (i, "/".join(missing[i])) for i in sorted(missing))))
+
+    def detect(self, imgs, aligner=None):
+        """imgs: uint8 photos, a list of [H_i, W_i, 3] (any mix of sizes) or one [B, H, W, 3] ->
+        {"points" float32 [B, 4, 2] (x, y) of the left eye, right eye, nose and mouth centre in the
+        128 x 128 frame, "points_photo" the same in each photo's own pixels (times float32 (W / 128,
+        H / 128)), "score" float32 [B, 4], "anchor" int32 [B, 4], "boxes" int32 [B, 4, 4] (left, upper,
+        right, lower: FaceBatcher.from_points takes them), "status" int32 [B] (tpgan_ops.ssd_landmarks),
+        "u8_128" uint8 [B, 128, 128, 3]}.  The status read is the call's only copy to the host.
+
+        aligner: a FaceAligner (128 x 128 output) or None.  With one the call is two passes: detect on
+        the squashed photo as above, fit the similarity transform from the aligner's template to those
+        points in the photo's own pixels and warp the photo through it, then detect again on the
+        aligned faces.  The dict then describes the ALIGNED faces ("u8_128", "points", "score",
+        "anchor", "boxes" and "status" are the second pass's) and adds "matrix" float32 [B, 2, 3]
+        (aligned frame -> photo pixels), "align_status" int32 [B] (FaceAligner.align) and "points_photo",
+        the second pass's points mapped through matrix.  on_missing and the NaN rule hold for both
+        passes; a face whose fit failed (align_status bit 0 or 1) raises ValueError.  The three status
+        arrays reach the host in one copy."""
+        imgs = _u8_images(self.device, imgs, "imgs")
+        B = len(imgs)
+        if B == 0:
+            raise ValueError("imgs holds no photos")
+        if aligner is not None:
+            if not isinstance(aligner, FaceAligner):
+                raise ValueError("aligner must be a FaceAligner or None, got %s" % type(aligner).__name__)
+            if aligner.device != self.device:
+                raise ValueError("aligner is on %s, the detector on %s" % (aligner.device, self.device))
+            if aligner.out_hw != (128, 128):
+                raise ValueError("the detector's frame is 128 x 128, the aligner's %s" % (aligner.out_hw,))
+        fb = self._batcher()
+        with torch.no_grad(), torch.cuda.device(self.device):
+            u8_128 = fb.resize(imgs, (128, 128))
+            points, score, anchor, boxes, status = self._decode(u8_128)
+            to_photo = torch.from_numpy((_photo_wh(imgs) / 128.0).astype(np.float32)).to(self.device)
+            points_photo = points * to_photo[:, None, :]
+            if aligner is None:
+                st = status.tolist()  # the one device-to-host copy
+            else:
+                al = aligner.align(imgs, points_photo, in_status=status)
+                u8_128, matrix = al["u8"], al["matrix"]
+                points, score, anchor, boxes, status2 = self._decode(u8_128)
+                m = matrix[:, None]  # [B, 1, 2, 3]: photo = M @ (x, y, 1)
+                points_photo = points[..., 0:1] * m[..., 0] + points[..., 1:2] * m[..., 1] + m[..., 2]
+                host = torch.cat([status, status2, al["status"]]).tolist()  # the one device-to-host copy
+                st, st2, ast = host[:B], host[B:2 * B], host[2 * B:]
+                status = status2
+        self._check_status(st)
+        if aligner is None:
+            return {"points": points, "points_photo": points_photo, "score": score, "anchor": anchor, "boxes": boxes,
+                    "status": status, "u8_128": u8_128}
+        FaceAligner.check_status(ast)
+        self._check_status(st2)
         return {"points": points, "points_photo": points_photo, "score": score, "anchor": anchor, "boxes": boxes,
-                "status": status, "u8_128": u8_128}
+                "status": status, "u8_128": u8_128, "matrix": matrix, "align_status": al["status"]}
 
     def accuracy(self, points, truth, status=None):
         """Pretrain.py's banded accuracy per face, float32 [B] (tpgan_ops.landmark_accuracy)."""
         return tpgan_ops.landmark_accuracy(points, truth, status)
+
+
+class FaceAligner:
+    """The step between the landmark detector and the generator: fit the similarity transform
+    (rotation, uniform scale, translation) from a template of the four crop centres onto the
+    points detected in a photo, and resample the photo through it, so that a small, off-centre or
+    tilted face reaches the generator in the frame it was trained on.  Two launches, nothing read
+    back (tpgan_ops.similarity_fit, tpgan_ops.affine_warp_u8).
+
+    template   float32 [4, 2]: (x, y) of the left eye, right eye, nose and mouth centre in the output
+               frame.  Required: derive it from the faces the generator was trained on
+               (template_from_landmarks).  It must be finite and its points must not all coincide.
+    out_hw     (height, width) of the aligned faces; the detector and the generator take (128, 128).
+    """
+
+    def __init__(self, template, device="cuda", out_hw=(128, 128)):
+        t = template.detach().cpu().numpy() if isinstance(template, torch.Tensor) else np.asarray(template)
+        if t.shape != (4, 2):
+            raise ValueError("template must be float32 [4, 2], got shape %s" % (t.shape,))
+        t = np.ascontiguousarray(t, np.float32)
+        if not np.isfinite(t).all():
+            raise ValueError("template holds a NaN or infinite coordinate")
+        qc = t - t.mean(0, dtype=np.float32)
+        spread = np.float32((qc * qc).sum(dtype=np.float32))
+        if not (np.isfinite(spread) and spread > 0):
+            raise ValueError("the template's points coincide: no scale or rotation can be fitted to them")
+        out_hw = (int(out_hw[0]), int(out_hw[1]))
+        if not (1 <= out_hw[0] <= 4096 and 1 <= out_hw[1] <= 4096):
+            raise ValueError("out_hw sides must be in 1..4096, got %s" % (out_hw,))
+        self.template = t
+        self.out_hw = out_hw
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+
+    @staticmethod
+    def template_from_landmarks(lm68, scale=None):
+        """The mean of the four crop centres over a set of faces -> float32 [4, 2] (numpy), in the frame
+        the landmarks are in.  lm68: float32 [N, 68, 2] landmarks of training faces; scale: float32
+        [N, 2] (sx, sy) per face, e.g. 128 / size for photos that are resized to 128 x 128, or None.
+        The centres are FaceBatcher.landmark_boxes's reduction: float32 means of the
+        FIVE_PTS_IDX_REPAIRED index ranges summed in index order, times scale, the two mouth corners
+        averaged.  The mean over the faces is taken in float64 and rounded once."""
+        from DataAndDataset import FIVE_PTS_IDX_REPAIRED
+        lm = lm68.detach().cpu().numpy() if isinstance(lm68, torch.Tensor) else np.asarray(lm68)
+        if lm.ndim != 3 or lm.shape[0] < 1 or lm.shape[1] < 55 or lm.shape[2] != 2:
+            raise ValueError("lm68 must be float32 [N, 68, 2] with N >= 1, got shape %s" % (lm.shape,))
+        lm = lm.astype(np.float32)
+        n = lm.shape[0]
+        five = np.empty((n, 5, 2), np.float32)
+        for j, (lo, hi) in enumerate(FIVE_PTS_IDX_REPAIRED):
+            acc = np.zeros((n, 2), np.float32)
+            for i in range(lo, hi + 1):
+                acc = acc + lm[:, i]
+            five[:, j] = acc / np.float32(hi + 1 - lo)
+        if scale is not None:
+            sc = scale.detach().cpu().numpy() if isinstance(scale, torch.Tensor) else np.asarray(scale)
+            if sc.shape != (n, 2):
+                raise ValueError("scale must be float32 [%d, 2], got shape %s" % (n, sc.shape))
+            five = five * sc.astype(np.float32)[:, None, :]
+        centres = five[:, :4].copy()
+        centres[:, 3] = (five[:, 3] + five[:, 4]) / np.float32(2.0)
+        if not np.isfinite(centres).all():
+            bad = sorted(set(np.nonzero(~np.isfinite(centres))[0].tolist()))
+            raise ValueError("a landmark of face(s) %s is NaN or infinite" % bad)
+        return centres.astype(np.float64).mean(0).astype(np.float32)
+
+    @staticmethod
+    def check_status(status):
+        """ValueError naming the faces whose fit failed (bit 0: a point is NaN, infinite or beyond
+        1e9; bit 1: the fitted transform is degenerate or out of range).  status: host ints."""
+        bad = [i for i, v in enumerate(status) if v & 1]
+        if bad:
+            raise ValueError(_BAD_ALIGN % (bad, "a detected point is NaN, infinite or beyond 1e9"))
+        bad = [i for i, v in enumerate(status) if v & 2]
+        if bad:
+            raise ValueError(_BAD_ALIGN % (bad, "the fitted transform is degenerate or out of range (scale zero or "
+                                                "above 32, translation beyond 16384 pixels)"))
+
+    def align(self, imgs, points_photo, in_status=None):
+        """imgs: uint8 photos, a list of [H_i, W_i, 3] or one [B, H, W, 3]; points_photo: float32
+        [B, 4, 2] device tensor, the four points in each photo's own pixels; in_status: int32 [B]
+        (the detector's status) or None -> {"u8" uint8 [B, out_h, out_w, 3], "matrix" float32
+        [B, 2, 3] (aligned frame -> photo pixels), "matrix_q16" int32 [B, 2, 3] (what the warp used),
+        "status" int32 [B]: the fit's bits 0..2 ORed with the warp's bit 3 (tpgan_ops.similarity_fit,
+        tpgan_ops.affine_warp_u8)}.  Nothing is read back: a face with bit 0 or 1 was warped by the
+        identity, and the caller decides (check_status)."""
+        imgs = _u8_images(self.device, imgs, "imgs")
+        B = len(imgs)
+        if not isinstance(points_photo, torch.Tensor) or points_photo.dtype != torch.float32 \
+                or tuple(points_photo.shape) != (B, 4, 2):
+            raise ValueError("points_photo must be a float32 [%d, 4, 2] device tensor" % B)
+        if points_photo.device != self.device:
+            raise ValueError("points_photo must be on %s, got %s" % (self.device, points_photo.device))
+        if B == 0:
+            raise ValueError("imgs holds no photos")
+        with torch.no_grad(), torch.cuda.device(self.device):
+            matrix, q16, fit_status = tpgan_ops.similarity_fit(points_photo, self.template, in_status)
+            u8, warp_status = tpgan_ops.affine_warp_u8(imgs, q16, self.out_hw)
+            return {"u8": u8, "matrix": matrix, "matrix_q16": q16, "status": fit_status | warp_status}

@@ -152,6 +152,12 @@ EXPORTS = {
                             [ctypes.c_int32] * 3 + [ctypes.c_int64] + [ctypes.c_int32] * 2 + [ctypes.c_int64] * 3),
     "tpg_resize_u8": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
                                        ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "tpg_similarity_fit": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 7),
+    "tpg_warp_job_bytes": (ctypes.c_size_t, []),
+    "tpg_warp_pack_job": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p] +
+                          [ctypes.c_int32] * 3 + [ctypes.c_int64] + [ctypes.c_int32] * 2),
+    "tpg_affine_warp_u8": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                            ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "tpg_denorm_u8": (ctypes.c_int32, [ctypes.c_int32] * 4 + [TpgTensor, ctypes.c_void_p, ctypes.c_void_p]),
     "tpg_image_metrics_workspace": (ctypes.c_int64, [ctypes.c_int32] * 4),
     "tpg_image_metrics_u8": (ctypes.c_int32, [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 5 +

@@ -2229,6 +2229,100 @@ def landmark_accuracy(pred, truth, status=None, thresholds=(5, 10, 18, 30, 45), 
     return acc
 
 
+# ---- face alignment (tpg_align.hip): detected points -> a similarity transform onto a template ->
+# the photo resampled into the generator's frame.  Two launches on the current stream, no host
+# synchronisation; the warp reads the fit's 16.16 matrices on the device.  None is differentiable.
+def similarity_fit(points, template, in_status=None):
+    """Least-squares rotation + uniform scale + translation (no reflection) mapping the template
+    points (K host floats [K, 2] in the output frame, 2 <= K <= 8, the same for every face) onto
+    each face's points (float32 [B, K, 2] device tensor, photo pixels) -> (matrix float32 [B, 2, 3]
+    with photo = M @ (x, y, 1), matrix_q16 int32 [B, 2, 3] = rint(matrix * 65536), status int32 [B]).
+    status bit 0: a point is NaN, infinite or beyond 1e9; bit 1: the fit is degenerate or out of
+    range (scale zero, not finite or > 32, |t| >= 16384); bit 2: in_status (int32 [B], e.g.
+    ssd_landmarks's) was non-zero.  A face with bit 0 or 1 gets the identity.  (tpg_similarity_fit)"""
+    fn = "similarity_fit"
+    _lm_arg(fn, "points", points, "[B, K, 2]", lambda t: t.dtype == torch.float32 and t.dim() == 3 and t.shape[2] == 2)
+    B, K = points.shape[0], points.shape[1]
+    tmpl = torch.as_tensor(template).detach().to("cpu", torch.float32)
+    if tmpl.dim() != 2 or tuple(tmpl.shape) != (K, 2):
+        raise ValueError("%s: template must hold [%d, 2] points like points, got %s" % (fn, K, tuple(tmpl.shape)))
+    if not 2 <= K <= 8:
+        raise ValueError("%s: 2..8 points per face, got %d" % (fn, K))
+    if in_status is not None:
+        if not isinstance(in_status, torch.Tensor) or in_status.dtype != torch.int32 or tuple(in_status.shape) != (B,):
+            raise ValueError("%s: in_status must be an int32 [%d] tensor" % (fn, B))
+        if in_status.device != points.device:
+            raise ValueError("%s: in_status must be on %s, got %s" % (fn, points.device, in_status.device))
+    lib = load()
+    with torch.no_grad(), torch.cuda.device(points.device):
+        points = points.detach().contiguous()
+        in_status = in_status.contiguous() if in_status is not None else None
+        matrix = torch.empty(B, 2, 3, dtype=torch.float32, device=points.device)
+        q16 = torch.empty(B, 2, 3, dtype=torch.int32, device=points.device)
+        status = torch.empty(B, dtype=torch.int32, device=points.device)
+        host = (ctypes.c_float * (2 * K))(*tmpl.flatten().tolist())
+        check(lib.tpg_similarity_fit(B, K, points.data_ptr(), host, in_status.data_ptr() if in_status is not None
+                                     else None, matrix.data_ptr(), q16.data_ptr(), status.data_ptr(), stream_ptr()))
+    return matrix, q16, status
+
+
+def _warp_src(fn, name, t):
+    """(pointer, H, W, row stride in bytes) of a uint8 [H, W, 3] device view whose pixels are packed
+    RGB; the rows may be any W*3 bytes or more apart (a crop of a wider image is taken as it is)."""
+    if t.shape[-1] != 3:
+        raise ValueError("%s: %s must have 3 interleaved bands (RGB, HWC), got %d" % (fn, name, t.shape[-1]))
+    H, W = t.shape[-3], t.shape[-2]
+    if not (1 <= H <= 4096 and 1 <= W <= 4096):
+        raise ValueError("%s: %s: sides must be in 1..4096, got %dx%d" % (fn, name, W, H))
+    s = t.stride()[-3:]
+    if s[2] != 1 or (W > 1 and s[1] != 3) or (H > 1 and s[0] < W * 3):
+        raise ValueError("%s: %s must have packed RGB pixels and rows at least W*3 bytes apart, got strides %s"
+                         % (fn, name, tuple(s)))
+    return H, W, s[0] if H > 1 else W * 3
+
+
+def affine_warp_u8(imgs, matrix_q16, out_hw=(128, 128)):
+    """Every photo resampled through its own 16.16 affine matrix (output frame -> photo pixels)
+    -> (uint8 [B, out_h, out_w, 3], status int32 [B]).  imgs: a list of uint8 [H_i, W_i, 3] device
+    tensors (any mix of sizes) or one [B, H, W, 3]; row strides are honoured, not copied away.
+    matrix_q16: int32 [B, 2, 3] (or [B, 6]) device tensor (m00, m01, tx, m10, m11, ty), any affine
+    map.  n x n bilinear sub-samples per output pixel, n the smallest of 1..16 that covers the map's
+    shrink; status bit 3 (8): the map shrinks by more than 16, the output is undersampled.  Integer
+    arithmetic, edge replicate; one launch whatever the sizes are.  (tpg_affine_warp_u8)"""
+    fn = "affine_warp_u8"
+    out_h, out_w = int(out_hw[0]), int(out_hw[1])
+    if not (1 <= out_h <= 4096 and 1 <= out_w <= 4096):
+        raise ValueError("%s: output sides must be in 1..4096, got %dx%d" % (fn, out_w, out_h))
+    if not isinstance(matrix_q16, torch.Tensor) or matrix_q16.dtype != torch.int32 or not matrix_q16.is_cuda:
+        raise ValueError("%s: matrix_q16 must be an int32 [B, 2, 3] device tensor" % fn)
+    dev = matrix_q16.device
+    views = list(imgs.unbind(0)) if isinstance(imgs, torch.Tensor) and imgs.dim() == 4 else list(imgs)
+    B = len(views)
+    if B > 65535:
+        raise ValueError("%s: at most 65535 photos per call, got %d" % (fn, B))
+    if matrix_q16.numel() != B * 6 or matrix_q16.shape[0] != B:
+        raise ValueError("%s: matrix_q16 must hold [%d, 2, 3] entries, got %s" % (fn, B, tuple(matrix_q16.shape)))
+    lib = load()
+    jb = lib.tpg_warp_job_bytes()
+    jobs = (ctypes.c_uint8 * (max(B, 1) * jb))()
+    for i, t in enumerate(views):
+        name = "imgs[%d]" % i
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3:
+            raise ValueError("%s: %s must be a uint8 [H, W, 3] device tensor" % (fn, name))
+        if t.device != dev:
+            raise ValueError("%s: %s must be on %s (matrix_q16's device), got %s" % (fn, name, dev, t.device))
+        H, W, stride = _warp_src(fn, name, t)
+        check(lib.tpg_warp_pack_job(jobs, i, t.data_ptr(), H, W, 3, stride, out_h, out_w))
+    with torch.no_grad(), torch.cuda.device(dev):
+        out = torch.empty(B, out_h, out_w, 3, dtype=torch.uint8, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        if B:
+            jobs_dev = torch.frombuffer(jobs, dtype=torch.uint8).to(dev)
+            check(lib.tpg_affine_warp_u8(B, jobs_dev.data_ptr(), matrix_q16.contiguous().data_ptr(), out_h, out_w,
+                                         out.data_ptr(), status.data_ptr(), stream_ptr()))
+    return out, status
+
+
 # ---- inference image path (tpg_image.hip): [-1, 1] activations -> u8 HWC pixels, and the
 # validation metrics of a u8 result against the u8 ground truth.  Neither is differentiable.
 def denorm_u8(x):
