@@ -2,7 +2,7 @@
 // backward + bias gradient, strided copy / concat / dtype conversion, LocalFuser,
 // maxout, reflection-pad fold and the Adam update.  Each is a grid-stride loop over
 // channels-last elements so that consecutive lanes touch consecutive channels.
-#include "tpg_internal.h"
+#include "tpg_device.h"
 #include "../../include/tpgan.h"
 #include <stdlib.h>
 #include <string.h>
@@ -84,7 +84,7 @@ __device__ __forceinline__ void pack_halo_block_t(const PackArgs& p, int bn, int
   }
   __syncthreads();
   const int rl = t >> 2, pchunk = t & 3;
-  const int cl0 = (pchunk ^ pack_hswz(r0 + rl)) * EPC;
+  const int cl0 = (pchunk ^ swz64(r0 + rl)) * EPC;
   union { uint4 u; E e[EPC]; } o;
 #pragma unroll
   for (int e = 0; e < EPC; ++e) o.e[e] = (E)tile[cl0 + e][rl];

@@ -19,10 +19,9 @@
 // each split writes an fp32 partial slice, summed by the epilogue kernel (no atomics).
 //
 // LDS images use 64-byte pixel rows; the 16-byte chunk g of row p is stored at
-// g ^ (((p >> 2) & 1) << 1), which makes the ds_read_b128 fragment reads of both
-// operands bank-conflict free for any shift (checked exhaustively over the gfx950
-// ds_read_b128 lane groups).
-#include "tpg_internal.h"
+// g ^ swz64(p) (tpg_device.h), which makes the ds_read_b128 fragment reads of both
+// operands bank-conflict free for any shift.
+#include "tpg_device.h"
 #include <type_traits>
 #include <algorithm>
 #include <stdlib.h>
@@ -40,12 +39,6 @@
 #endif
 
 namespace tpg {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
-__device__ __forceinline__ int hswz(int row) { return ((row >> 2) & 1) << 1; }
 
 __host__ __device__ constexpr int halo_bnl(int bn) { return (bn + 127) / 128 * 128; }
 // epilogue: rows of the tile parked in LDS per pass (fp32, stride BN + 4): 64 on the
@@ -84,13 +77,6 @@ __device__ __forceinline__ u32x4 mask_chunk4(u32x4 v, int c0, int C) {
     }
   }
   return v;
-}
-
-__device__ __forceinline__ float h_act(float v, int act, float slope) { return tpg_act(v, act, slope); }
-
-__device__ __forceinline__ int h_refl(int i, int n) {
-  i = i < 0 ? -i : i;
-  return i >= n ? 2 * n - 2 - i : i;
 }
 
 // g = gy * act'(y) on one 16-byte chunk of each (the masked input-gradient mode)
@@ -262,7 +248,7 @@ __global__ __launch_bounds__(512) void halo_kernel(const Grouped<HaloArgs, NG> G
         const int ty = (int)p.fd_tilesw.div(trem), tx = trem - ty * tiles_w;
         const int hy = (int)p.fd_hw.div(hl), hx = hl - hy * HW;
         int gy = ty * TH * SH + p.dymin + hy, gx = tx * TW * SW + p.dxmin + hx;
-        if (p.pad_mode) { gy = h_refl(gy, p.A_H); gx = h_refl(gx, p.A_W); }
+        if (p.pad_mode) { gy = tpg_refl(gy, p.A_H); gx = tpg_refl(gx, p.A_W); }
         bool real = true;
         if (p.dil > 1) {  // zero-inserted grid: only multiples of dil are pixels of A
           real = gy >= 0 && gx >= 0 && gy % p.dil == 0 && gx % p.dil == 0;
@@ -305,7 +291,7 @@ __global__ __launch_bounds__(512) void halo_kernel(const Grouped<HaloArgs, NG> G
     for (int q = 0; q < HL; ++q) {
       const int idx = tid + 512 * q;
       const int hp = idx >> 2;
-      const int pos = hp * 4 + ((idx & 3) ^ hswz(hp));
+      const int pos = hp * 4 + ((idx & 3) ^ swz64(hp));
       u32x4 v = hreg[q];
       if constexpr (MASK) {
         if (hp < HPT) v = act_mask_chunk<E>(v, H[pos], p.mact, p.mslope);  // y chunk, DMA'd in place
@@ -319,7 +305,7 @@ __global__ __launch_bounds__(512) void halo_kernel(const Grouped<HaloArgs, NG> G
   };
   // mask mode: LDS-DMA of y's chunks of k-step ks into halo buffer buf, at the positions the
   // halo chunks will take (lane-linear DMA: the lane landing at position idx fetches pixel
-  // idx >> 2, logical chunk (idx & 3) ^ hswz(pixel)); store_halo reads them back, masks and
+  // idx >> 2, logical chunk (idx & 3) ^ swz64(pixel)); store_halo reads them back, masks and
   // overwrites them.  Invalid pixels fetch element 0 (their g is zeroed anyway).
   const E* Mg = reinterpret_cast<const E*>(p.M);
   auto issue_m = [&](int ks, int buf) {
@@ -330,7 +316,7 @@ __global__ __launch_bounds__(512) void halo_kernel(const Grouped<HaloArgs, NG> G
       for (int q = 0; q < HL; ++q) {
         const int idx = tid + 512 * q;
         const int hp = idx >> 2;
-        const int c = cbase + (((idx & 3) ^ hswz(hp)) * EPC);
+        const int c = cbase + (((idx & 3) ^ swz64(hp)) * EPC);
         const E* src = Mg + ((mpix[q] >= 0 && c < p.C) ? mpix[q] + c : 0);
         if ((512 * q + 64 * wave) / 4 < hcap)  // wave-uniform; hcap % 16 == 0: the instruction stays inside the buffer
           lds_dma16(src, __builtin_amdgcn_readfirstlane(lds_addr(dst + (512 * q + 64 * wave) * 16)));
@@ -395,7 +381,7 @@ __global__ __launch_bounds__(512) void halo_kernel(const Grouped<HaloArgs, NG> G
     u32x4 af[MREP];
 #pragma unroll
     for (int m = 0; m < MREP; ++m) {
-      // byte offset hp * 64 + 16 * (chunk ^ hswz(hp)) = (hp << 6) + ((chunk << 4) ^ ((hp << 3) & 32))
+      // byte offset hp * 64 + 16 * (chunk ^ swz64(hp)) = (hp << 6) + ((chunk << 4) ^ ((hp << 3) & 32))
       const int hp = hbase[m] + tl;
       af[m] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(H) + (hp << 6) + (gc ^ ((hp << 3) & 32)));
     }
@@ -406,7 +392,7 @@ __global__ __launch_bounds__(512) void halo_kernel(const Grouped<HaloArgs, NG> G
 #pragma unroll
     for (int n = 0; n < NREP; ++n) {
       const int r = wn * WTN + n * 16 + l16;
-      bf[n] = Wl[r * 4 + (g ^ hswz(r))];
+      bf[n] = Wl[r * 4 + (g ^ swz64(r))];
     }
 #pragma unroll
     for (int n = 0; n < NREP; ++n)
@@ -449,9 +435,9 @@ __global__ __launch_bounds__(512) void halo_kernel(const Grouped<HaloArgs, NG> G
           if (W) {
             yo = ((int64_t)(nimg * p.JH + j) * p.JW + i) * p.Nout;
           } else {
-            const int oy = p.oy0 + p.osy * j, ox = p.ox0 + p.osx * i;
-            yo = (int64_t)nimg * p.y_sn + (int64_t)oy * p.y_sh + (int64_t)ox * p.y_sw;
-            ro = (int64_t)nimg * p.r_sn + (int64_t)oy * p.r_sh + (int64_t)ox * p.r_sw;
+            const OutOff o = out_offsets(p, nimg, j, i);
+            yo = o.y;
+            ro = o.r;
           }
         }
       }
@@ -667,7 +653,7 @@ __global__ __launch_bounds__(512) void halo_kernel(const Grouped<HaloArgs, NG> G
             o.e[e] = (E)tpg_act_grad(v[e], (float)xx.e[e], p.xa_act, p.xa_slope);
         } else {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) o.e[e] = (E)h_act(v[e], p.act, p.slope);
+          for (int e = 0; e < 8; ++e) o.e[e] = (E)tpg_act(v[e], p.act, p.slope);
         }
         E* dst = Y + yo + col0;
         if (full && p.yvec) {
@@ -887,7 +873,7 @@ int launch_halo_group(const HaloArgs* a, int n, int dtype, int cfg, hipStream_t 
 
 // -------------------------------------------------------------- halo weight packing --
 // Wp[ks*ntaps + tap][ntile][BNL rows][4 chunks][EPC]: row r of N-tile nt is output
-// n' = nt*BN + r (zero when r >= BN or n' >= Nout); chunk' = chunk ^ hswz(r) holds
+// n' = nt*BN + r (zero when r >= BN or n' >= Nout); chunk' = chunk ^ swz64(r) holds
 // logical channels c = ks*KS + chunk*EPC + e of that tap.  A paired last k-step (half) has
 // ceil(ntaps / 2) slices after the full ones (pack_halo_item).
 // One thread per 16-byte chunk, 32-bit index math (the packed image is < 2^31 elements).

@@ -25,28 +25,18 @@
 // store into any (n, h, w) strided NHWC view (a channel slice implements zero-copy
 // output into a concat buffer).  Split-K blocks atomically add fp32 partials into a work
 // space instead; tpg_epilogue_kernel finishes them.
-#include "tpg_internal.h"
+#include "tpg_device.h"
 #include <type_traits>
 #include <algorithm>
 #include <string.h>
 
 namespace tpg {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-__device__ __forceinline__ float act_apply(float v, int act, float slope) { return tpg_act(v, act, slope); }
-
 template <typename E>
 __device__ __forceinline__ float ld_f(const E* p) { return (float)(*p); }
 
 template <typename E>
 __device__ __forceinline__ void st_f(E* p, float v) { *p = (E)v; }
-
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-  i = i < 0 ? -i : i;
-  return i >= n ? 2 * n - 2 - i : i;
-}
 
 template <int DT, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs p) {
@@ -121,7 +111,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs p) {
 #pragma unroll
     for (int q = 0; q < RA; ++q) {
       int iy = by[q] + dy, ix = bx[q] + dx;
-      if (p.pad_mode) { iy = reflect_idx(iy, p.A_H); ix = reflect_idx(ix, p.A_W); }
+      if (p.pad_mode) { iy = tpg_refl(iy, p.A_H); ix = tpg_refl(ix, p.A_W); }
       const bool ok = tap_ok && rv[q] && (unsigned)iy < (unsigned)p.A_H && (unsigned)ix < (unsigned)p.A_W && c < p.C;
       const int64_t off = a_base[q] + (int64_t)iy * p.a_sh + (int64_t)ix * p.a_sw + c;
       a_ok |= (ok ? 1u : 0u) << q;
@@ -241,9 +231,8 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs p) {
       int rem = row - n * JHJW;
       int j = p.div_jw.div(rem);
       int i = rem - j * p.JW;
-      int oy = p.oy0 + p.osy * j, ox = p.ox0 + p.osx * i;
-      int64_t yoff = (int64_t)n * p.y_sn + (int64_t)oy * p.y_sh + (int64_t)ox * p.y_sw;
-      int64_t roff = (int64_t)n * p.r_sn + (int64_t)oy * p.r_sh + (int64_t)ox * p.r_sw;
+      const OutOff o = out_offsets(p, n, j, i);
+      const int64_t yoff = o.y, roff = o.r;
 #pragma unroll
       for (int nr = 0; nr < NREP; ++nr) {
         const int col = n0 + wn * WTN + nr * 16 + r16;
@@ -254,7 +243,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs p) {
         } else {
           if (p.bias) v += p.bias[p.bias_mod ? col % p.bias_mod : col];
           if (R) v += p.res_scale * ld_f(R + roff + col);
-          st_f(Y + yoff + col, act_apply(v, p.act, p.slope));
+          st_f(Y + yoff + col, tpg_act(v, p.act, p.slope));
         }
       }
     }
@@ -292,7 +281,7 @@ __global__ __launch_bounds__(256) void epilogue_kernel(const Grouped<EpiArgs, NG
     int n = row / JHJW;
     int rem = row - n * JHJW;
     int j = rem / p.JW, i = rem - j * p.JW;
-    int oy = p.oy0 + p.osy * j, ox = p.ox0 + p.osx * i;
+    const OutOff o = out_offsets(p, n, j, i);
     float v[V];
     // slices summed in order z = 0, 1, ... (deterministic), their loads issued four at a time:
     // one at a time, every slice exposed a full memory latency (a k split of 8 -> ~8 of them)
@@ -326,8 +315,7 @@ __global__ __launch_bounds__(256) void epilogue_kernel(const Grouped<EpiArgs, NG
       for (; z < p.nslices; ++z) a += src[z * p.slice];
       v[0] = a;
     }
-    const int64_t yo = (int64_t)n * p.y_sn + (int64_t)oy * p.y_sh + (int64_t)ox * p.y_sw + col;
-    const int64_t ro = (int64_t)n * p.r_sn + (int64_t)oy * p.r_sh + (int64_t)ox * p.r_sw + col;
+    const int64_t yo = o.y + col, ro = o.r + col;
     if constexpr (V == 4 && sizeof(E) == 2) {
       // four 16-bit outputs as one 8-byte store (and an 8-byte residual load) when aligned
       // (the four halves are taken apart as scalars: this hipcc compiles
@@ -357,9 +345,9 @@ __global__ __launch_bounds__(256) void epilogue_kernel(const Grouped<EpiArgs, NG
             E o;
             if (XA) {
               const unsigned short x16 = (unsigned short)(e ? (xh >> 16) : (xh & 0xffffu));
-              o = (E)tpg_xa_grad(x, (float)__builtin_bit_cast(E, x16), p.xa_act, p.xa_slope);
+              o = (E)tpg_act_grad(x, (float)__builtin_bit_cast(E, x16), p.xa_act, p.xa_slope);
             } else {
-              o = (E)act_apply(x, p.act, p.slope);
+              o = (E)tpg_act(x, p.act, p.slope);
             }
             const unsigned short o16 = __builtin_bit_cast(unsigned short, o);
             packed |= (uint32_t)o16 << (16 * e);
@@ -375,8 +363,8 @@ __global__ __launch_bounds__(256) void epilogue_kernel(const Grouped<EpiArgs, NG
       float x = v[u];
       if (p.bias) x += p.bias[p.bias_mod ? (col + u) % p.bias_mod : col + u];
       if (R) x += p.res_scale * ld_f(R + ro + u);
-      st_f(Y + yo + u, XA ? tpg_xa_grad(x, ld_f(XA + yo + u), p.xa_act, p.xa_slope)
-                          : act_apply(x, p.act, p.slope));
+      st_f(Y + yo + u, XA ? tpg_act_grad(x, ld_f(XA + yo + u), p.xa_act, p.xa_slope)
+                          : tpg_act(x, p.act, p.slope));
     }
   }
 }

@@ -55,11 +55,6 @@ __device__ __forceinline__ float tpg_act_grad(float g, float y, int act, float s
   return g;
 }
 
-// the input-gradient epilogue's producer act' (desc.in_act)
-__device__ __forceinline__ float tpg_xa_grad(float g, float x, int act, float slope) {
-  return tpg_act_grad(g, x, act, slope);
-}
-
 // Fast unsigned division by a runtime constant for n, d < 2^31 (round-up method):
 // s = ceil(log2 d), mul = ceil(2^(31+s) / d) < 2^32, q = umulhi(n, mul) >> (s - 1).
 struct FastDiv {
@@ -279,110 +274,7 @@ struct PackJob {
   int nblocks;
 };
 
-__device__ __forceinline__ int pack_hswz(int row) { return ((row >> 2) & 1) << 1; }
-
-// igemm layout: item = (n', unit) -> 16 consecutive elements of Wp row n'
-template <typename E>
-__device__ __forceinline__ void pack_igemm_item(const PackArgs& p, int idx) {
-  const int np = idx / p.nunits;
-  const int unit = idx - np * p.nunits;
-  const int tap = unit / p.upt;
-  const int cbase = (unit - tap * p.upt) * 16;
-  E out[16];
-  const bool ok = np < p.Nreal && tap < p.ntaps;
-  int a = 0, b = 0, r = ok ? p.tr[tap] : 0, s = ok ? p.ts[tap] : 0;
-  if (p.nmode == 0) a = np;
-  else if (p.nmode == 1) b = np;
-  else {
-    const int rs = np / p.comp_c, ch = np - rs * p.comp_c;
-    r = rs / p.comp_kw; s = rs - r * p.comp_kw;
-    if (p.nmode == 2) b = ch; else a = ch;
-  }
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int cp = cbase + e;
-    float v = 0.f;
-    if (ok && cp < p.Creal) {
-      int aa = a, bb = b, rr = r, ss = s;
-      if (p.cmode == 0) aa = cp;
-      else if (p.cmode == 1) bb = cp;
-      else {
-        const int rs = cp / p.comp_c, ch = cp - rs * p.comp_c;
-        rr = rs / p.comp_kw; ss = rs - rr * p.comp_kw;
-        if (p.cmode == 2) bb = ch; else aa = ch;
-      }
-      v = p.W[(int64_t)aa * p.w_sa + (int64_t)bb * p.w_sb + (int64_t)rr * p.w_sr + (int64_t)ss * p.w_ss];
-    }
-    out[e] = (E)v;
-  }
-  uint4* dst = reinterpret_cast<uint4*>(reinterpret_cast<E*>(p.Wp) + (int64_t)idx * 16);
-  const uint4* src = reinterpret_cast<const uint4*>(out);
-#pragma unroll
-  for (int q = 0; q < (int)(16 * sizeof(E) / 16); ++q) dst[q] = src[q];
-}
-
-// halo layout: Wp[ks*ntaps + tap][ntile][bnl rows][4 chunks][EPC]; item = one 16-byte chunk;
-// row r of N-tile nt is n' = nt*bn + r, chunk' = chunk ^ hswz(r)
-template <typename E>
-__device__ __forceinline__ void pack_halo_item(const PackArgs& p, int bn, int bnl, int ntiles, int idx) {
-  constexpr int EPC = 16 / sizeof(E);
-  constexpr int ROW = 4 * EPC;
-  const int pchunk = idx & 3;
-  int rr = idx >> 2;
-  const int r = rr % bnl;
-  rr /= bnl;
-  const int nt = rr % ntiles;
-  rr /= ntiles;
-  // step rr: k-step rr / ntaps, tap rr % ntaps; past the full k-steps of a paired image (half:
-  // the last k-step holds <= 16 live channels) step j carries taps 2j (logical chunks 0, 1) and
-  // 2j + 1 (chunks 2, 3), channels 0..15 of that k-step each (tpg_halo.hip compute)
-  const int lc = pchunk ^ pack_hswz(r);
-  const int nfull = (p.half ? p.hnks - 1 : p.hnks) * p.ntaps;
-  int tap, c0;
-  bool tap_ok = true;
-  if (rr < nfull) {
-    tap = rr % p.ntaps;
-    c0 = (rr / p.ntaps) * ROW + lc * EPC;
-  } else {
-    tap = 2 * (rr - nfull) + (lc >> 1);
-    c0 = (p.hnks - 1) * ROW + (lc & 1) * EPC;
-    tap_ok = tap < p.ntaps;
-    if (!tap_ok) tap = 0;
-  }
-  const int np = nt * bn + r;
-  union { uint4 u; E e[EPC]; } o;
-  const bool row_ok = r < bn && np < p.Nreal && tap_ok;
-  const int tr = p.tr[tap], ts = p.ts[tap];
-  const int64_t base = (int64_t)tr * p.w_sr + (int64_t)ts * p.w_ss +
-                       (p.nmode == 0 ? (int64_t)np * p.w_sa : (int64_t)np * p.w_sb);
-  const int64_t cstride = p.cmode == 0 ? p.w_sa : p.w_sb;
-  const float* src = p.W + base + (int64_t)c0 * cstride;
-  if (cstride == 1 && row_ok && c0 + EPC <= p.Creal && ((uintptr_t)src % 16) == 0) {
-    // contiguous input channels (the forward images of channels-last weights): 16-byte loads
-#pragma unroll
-    for (int q = 0; q < EPC / 4; ++q) {
-      const float4 v = reinterpret_cast<const float4*>(src)[q];
-      o.e[4 * q] = (E)v.x; o.e[4 * q + 1] = (E)v.y; o.e[4 * q + 2] = (E)v.z; o.e[4 * q + 3] = (E)v.w;
-    }
-  } else if (cstride == 1 && row_ok && c0 + EPC <= p.Creal && ((uintptr_t)src % 8) == 0) {
-    // (an even channel count that is not a multiple of 4 -- 206 -- leaves every other tap's
-    // rows 8-byte aligned only: 8-byte loads instead of 4-byte ones; G's re-pack 0.489 ->
-    // 0.470 ms, tools/bench_opt.py, gpurun r06r)
-#pragma unroll
-    for (int q = 0; q < EPC / 2; ++q) {
-      const float2 v = reinterpret_cast<const float2*>(src)[q];
-      o.e[2 * q] = (E)v.x; o.e[2 * q + 1] = (E)v.y;
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) {
-      const int c = c0 + e;
-      o.e[e] = (E)((row_ok && c < p.Creal) ? p.W[base + (int64_t)c * cstride] : 0.f);
-    }
-  }
-  reinterpret_cast<uint4*>(p.Wp)[idx] = o.u;
-}
-
+// (the pack items -- one igemm unit, one 16-byte chunk of a halo image -- are device code: tpg_device.h)
 int launch_pack_many(const PackJob* jobs_dev, int n, int nblocks, hipStream_t s);
 
 

@@ -10,13 +10,13 @@
 // counted vmcnt + barrier per k-step, 4 waves on 64/128 x 64/128 tiles (small M x N problems
 // get enough blocks without splitting K), and the halo kernel's packed weight image and
 // epilogue conventions (bias, residual, activation through LDS; or fp32 partial slices for a
-// k split, finished by the split-K epilogue kernel).
+// k split, finished by the split-K epilogue kernel; the epilogue is a copy of tpg_halo.hip's).
 //
 // LDS rows are 64 bytes (one k-step of one pixel / one output channel); chunk g of row r sits
-// at g ^ (((r >> 2) & 1) << 1), the halo kernel's conflict-free image -- the packed weights are
+// at g ^ swz64(r) (tpg_device.h), the halo kernel's conflict-free image -- the packed weights are
 // stored pre-swizzled that way, so their DMA is a straight copy; the A rows are swizzled by
 // choosing each lane's SOURCE chunk.
-#include "tpg_internal.h"
+#include "tpg_device.h"
 #include <type_traits>
 
 namespace tpg {
@@ -25,10 +25,6 @@ namespace tpg {
 #define PW_NST 4  // LDS ring stages (three k-steps in flight)
 #endif
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
-__device__ __forceinline__ int pw_swz(int row) { return ((row >> 2) & 1) << 1; }
 __device__ u32x4 pw_zero[4];  // the zero line of out-of-grid A rows (64 bytes)
 
 __host__ __device__ constexpr int pw_stage_bytes(int bm, int bn) { return (bm + bn) * 64; }
@@ -80,7 +76,7 @@ __global__ __launch_bounds__(256, 2) void pw_kernel(const HaloArgs p) {
 
   // ---- A: this thread's DMA chunks (piece j of wave w covers 16-byte slots (j*4 + w)*64 + lane
   // of the A image, slot s = row * 4 + physical chunk; the source is the row's logical chunk
-  // (s & 3) ^ swz(row)) of the row's pixel shifted by the step's tap; rows outside the grid and
+  // (s & 3) ^ swz64(row)) of the row's pixel shifted by the step's tap; rows outside the grid and
   // taps outside the image read a zero line (LDS-DMA through inline asm, as the halo kernel's
   // weights: the builtin would make the compiler wait for every DMA in flight before each
   // fragment read)
@@ -98,7 +94,7 @@ __global__ __launch_bounds__(256, 2) void pw_kernel(const HaloArgs p) {
 #pragma unroll
   for (int j = 0; j < PA; ++j) {
     const int s = (j * 4 + wave) * 64 + lane;
-    const int row = s >> 2, c = (s & 3) ^ pw_swz(row);
+    const int row = s >> 2, c = (s & 3) ^ swz64(row);
     const int q = m0 + row;
     abase[j] = nullptr;
     agy[j] = agx[j] = 0;
@@ -128,7 +124,12 @@ __global__ __launch_bounds__(256, 2) void pw_kernel(const HaloArgs p) {
 #pragma unroll
     for (int j = 0; j < PA; ++j) {
       int y = agy[j] + (tap >> 16), x = agx[j] + (tap & 0xffff);
-      if (pad_mode) {  // (reflect: the mirrored pixel)
+      // (reflect: the mirrored pixel.  Written out, not tpg_refl: the helper folds |i| a second
+      // time where this form does not, and with it this loop's code is not the measured one --
+      // 12 to 23 instructions shorter per instance; swap it in together with a timing of the
+      // reflect-padded layers, as with the row-table and slice-store code below, whose shared
+      // forms -- out_offsets; a group-store helper -- move this kernel's register allocation)
+      if (pad_mode) {
         y = y < 0 ? -y : (y >= A_H ? 2 * A_H - 2 - y : y);
         x = x < 0 ? -x : (x >= A_W ? 2 * A_W - 2 - x : x);
       }
@@ -185,7 +186,7 @@ __global__ __launch_bounds__(256, 2) void pw_kernel(const HaloArgs p) {
 #pragma unroll
       for (int n = 0; n < NREP; ++n) {
         const int r = wn * WTN + n * 16 + l16;
-        bf[n] = B[r * 4 + (g ^ pw_swz(r))];
+        bf[n] = B[r * 4 + (g ^ swz64(r))];
       }
 #pragma unroll
       for (int n = 0; n < NREP; ++n)
@@ -199,7 +200,7 @@ __global__ __launch_bounds__(256, 2) void pw_kernel(const HaloArgs p) {
   }
   TPG_TL_MARK(2);
 
-  // ---- epilogue through LDS (the halo kernel's): rows parked as fp32, then 8-channel groups
+  // ---- epilogue through LDS (the halo kernel's form): rows parked as fp32, then 8-channel groups
   constexpr int LDW = BN + 4, CG = BN / 8, NV = 8 * (int)sizeof(E) / 16;
   __syncthreads();
   int64_t* s_off = reinterpret_cast<int64_t*>(lds);              // [BM][2] out / residual offsets
@@ -311,7 +312,7 @@ __global__ __launch_bounds__(256, 2) void pw_kernel(const HaloArgs p) {
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e)
-        o.e[e] = (E)tpg_xa_grad(v[e], (float)xx.e[e], p.xa_act, p.xa_slope);
+        o.e[e] = (E)tpg_act_grad(v[e], (float)xx.e[e], p.xa_act, p.xa_slope);
     } else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) o.e[e] = (E)tpg_act(v[e], p.act, p.slope);

@@ -13,32 +13,10 @@
 //   f32:  one ds_read_b32 per v_mfma_f32_16x16x4_f32 operand
 // Split-K partials are added with no-return fp32 atomics into the caller's fp32 dW
 // (lanes 0..15 hit 16 consecutive b, i.e. 64 contiguous bytes on a channels-last weight).
-#include "tpg_internal.h"
+#include "tpg_device.h"
 #include <type_traits>
 
 namespace tpg {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-__device__ __forceinline__ int refl(int i, int n) {
-  i = i < 0 ? -i : i;
-  return i >= n ? 2 * n - 2 - i : i;
-}
-
-// XOR swizzle of the 16-byte chunk index inside an LDS row (see header comment of the
-// planner for the conflict analysis): bf16 rows read by ds_read_b64_tr_b16 take 8 rows
-// {0..3, 8..11} per 32-lane half; f32 rows read by ds_read_b32 take 2 rows per half.
-template <bool BF, int W>
-__device__ __forceinline__ int swz(int row, int chunk) {
-  if constexpr (BF) {
-    if constexpr (W == 64) return chunk ^ (((((row >> 1) & 1) | (((row >> 3) & 1) << 1))) << 1);
-    else return chunk ^ ((((row & 3) | (((row >> 3) & 1) << 2))) << 1);
-  } else {
-    return chunk ^ ((row & 1) << 2);
-  }
-}
 
 template <int DT, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs p) {
@@ -72,6 +50,10 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs p) {
 
   __syncthreads();
   const int dy = s_dy[tap], dx = s_dx[tap];
+  // XOR swizzle of the 16-byte chunk index inside an A / B row of the LDS image (tpg_device.h):
+  // 16-bit rows (BM / BN elements: 128 or 256 bytes) are read transposed, fp32 rows by ds_read_b32
+  auto swz_a = [](int row) { if constexpr (BF) return tr_swz<2 * BM>(row); else return f32_swz(row); };
+  auto swz_b = [](int row) { if constexpr (BF) return tr_swz<2 * BN>(row); else return f32_swz(row); };
 
   uint4 ra[LA], rb[LB];
   uint32_t okA = 0, okB = 0;
@@ -116,7 +98,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs p) {
       int py = p.div_pw.div(rem);
       int px = rem - py * p.PW;
       int qy = py * p.qst_h + dy, qx = px * p.qst_w + dx;
-      if (p.pad_mode) { qy = refl(qy, p.QH); qx = refl(qx, p.QW); }
+      if (p.pad_mode) { qy = tpg_refl(qy, p.QH); qx = tpg_refl(qx, p.QW); }
       ok = ok && (unsigned)qy < (unsigned)p.QH && (unsigned)qx < (unsigned)p.QW;
       const int64_t off = (int64_t)n * p.q_sn + (int64_t)qy * p.q_sh + (int64_t)qx * p.q_sw + c;
       okB |= (ok ? 1u : 0u) << q;
@@ -145,7 +127,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs p) {
         v = mask_chunk<EPC>(v, a0 + ch * EPC, p.Ca);
         if (!((okA >> q) & 1u)) v = make_uint4(0, 0, 0, 0);
       }
-      As[row * CPR_A + swz<BF, BM>(row, ch)] = v;
+      As[row * CPR_A + (ch ^ swz_a(row))] = v;
     }
 #pragma unroll
     for (int q = 0; q < LB; ++q) {
@@ -156,7 +138,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs p) {
         v = mask_chunk<EPC>(v, b0 + ch * EPC, p.Cb);
         if (!((okB >> q) & 1u)) v = make_uint4(0, 0, 0, 0);
       }
-      Bs[row * CPR_B + swz<BF, BN>(row, ch)] = v;
+      Bs[row * CPR_B + (ch ^ swz_b(row))] = v;
     }
   };
 
@@ -183,7 +165,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs p) {
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
           const int row = 8 * g + 4 * hh + q;
-          const char* base = reinterpret_cast<const char*>(As + row * CPR_A + swz<BF, BM>(row, col >> 3));
+          const char* base = reinterpret_cast<const char*>(As + row * CPR_A + ((col >> 3) ^ swz_a(row)));
           base += (col & 7) * 2;
           h[hh] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base));
         }
@@ -196,7 +178,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs p) {
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
           const int row = 8 * g + 4 * hh + q;
-          const char* base = reinterpret_cast<const char*>(Bs + row * CPR_B + swz<BF, BN>(row, col >> 3));
+          const char* base = reinterpret_cast<const char*>(Bs + row * CPR_B + ((col >> 3) ^ swz_b(row)));
           base += (col & 7) * 2;
           h[hh] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base));
         }
@@ -217,12 +199,12 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs p) {
 #pragma unroll
         for (int m = 0; m < MREP; ++m) {
           const int col = wm * WTM + m * 16 + l16;
-          av[m] = Af[row * BM + swz<BF, BM>(row, col >> 2) * 4 + (col & 3)];
+          av[m] = Af[row * BM + ((col >> 2) ^ swz_a(row)) * 4 + (col & 3)];
         }
 #pragma unroll
         for (int n = 0; n < NREP; ++n) {
           const int col = wn * WTN + n * 16 + l16;
-          bv[n] = Bf[row * BN + swz<BF, BN>(row, col >> 2) * 4 + (col & 3)];
+          bv[n] = Bf[row * BN + ((col >> 2) ^ swz_b(row)) * 4 + (col & 3)];
         }
 #pragma unroll
         for (int m = 0; m < MREP; ++m)

@@ -14,7 +14,7 @@
 // Channel tails: a 16-byte chunk that straddles Ca / Cb reads a few channels past the
 // tensor's real channels (inside the padded pixel row); they only feed dW rows / columns
 // that are never written.
-#include "tpg_internal.h"
+#include "tpg_device.h"
 #include <type_traits>
 #include <string.h>
 
@@ -25,36 +25,6 @@
 #endif
 
 namespace tpg {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4r;
-
-__device__ __forceinline__ int w2_refl(int i, int n) {
-  i = i < 0 ? -i : i;
-  return i >= n ? 2 * n - 2 - i : i;
-}
-
-// ds_read_b64_tr_b16 through inline asm (see compute()) at base + off, off in the
-// instruction's offset field (a constant once the caller's loops are unrolled)
-__device__ __forceinline__ s16x4 tr_read_o(const char* base, int off) {
-  s16x4 v;
-  const unsigned a = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)base;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(a), "i"(off));
-  return v;
-}
-
-// chunk swizzle of an LDS row of RB bytes (see tpg_wgrad.hip for the tr-read analysis)
-template <bool BF, int RB>
-__device__ __forceinline__ int w2_swz(int row) {
-  if constexpr (BF) {
-    if constexpr (RB == 128) return ((((row >> 1) & 1) | (((row >> 3) & 1) << 1))) << 1;
-    else return (((row & 3) | (((row >> 3) & 1) << 2))) << 1;
-  } else {
-    return (row & 1) << 2;
-  }
-}
 
 // Ring depth: TPG_W2_NST stages (default 3: two k-tiles in flight) where NST stages of the tile
 // fit in half the CU's LDS (two blocks per CU), else 3.
@@ -97,6 +67,11 @@ __global__ __launch_bounds__(512) void wgrad2_kernel(const Grouped<Wgrad2Args, N
 
   extern __shared__ __attribute__((aligned(16))) char lds[];  // [NST][STAGE]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  // chunk swizzle of an A / B row of the LDS image (tpg_device.h, with the tr-read analysis):
+  // 16-bit rows of 128, 256 or 512 bytes -- the 256-channel a-tile's 512-byte rows, two bank rows
+  // each, take the 256-byte rows' mask -- and fp32 rows
+  auto swz_a = [](int row) { if constexpr (BF) return tr_swz<(RBA < 256 ? RBA : 256)>(row); else return f32_swz(row); };
+  auto swz_b = [](int row) { if constexpr (BF) return tr_swz<(RBB < 256 ? RBB : 256)>(row); else return f32_swz(row); };
   // 1-D grid, logical block = (tile, tap, split), tile fastest.  Physical block b runs on
   // XCD b % 8; each XCD is handed a contiguous range of logical blocks, so the tiles that
   // share a pixel range (same dY rows, X rows shifted by the taps) meet in one L2.
@@ -127,7 +102,7 @@ __global__ __launch_bounds__(512) void wgrad2_kernel(const Grouped<Wgrad2Args, N
   for (int j = 0; j < GB; ++j) {
     const int o = (wave * GB + j) * 1024 + lane * 16;
     const int row = o / RBB, pc = (o % RBB) / 16;
-    const int lc = pc ^ w2_swz<BF, RBB>(row);
+    const int lc = pc ^ swz_b(row);
     const int col = b0 + lc * EPC;
     if constexpr (FLAT) {
       const int t = col / p.cbp;
@@ -151,7 +126,7 @@ __global__ __launch_bounds__(512) void wgrad2_kernel(const Grouped<Wgrad2Args, N
   for (int j = 0; j < GA; ++j) {
     const int o = (wave * GA + j) * 1024 + lane * 16;
     const int row = o / RBA, pc = (o % RBA) / 16;
-    const int lc = pc ^ w2_swz<BF, RBA>(row);
+    const int lc = pc ^ swz_a(row);
     prow[j] = row;
     pconst[j] = (int)((row * psw + a0 + lc * EPC) * ES);
   }
@@ -190,7 +165,7 @@ __global__ __launch_bounds__(512) void wgrad2_kernel(const Grouped<Wgrad2Args, N
     for (int j = 0; j < GA; ++j) {
       const int o = (wave * GA + j) * 1024 + lane * 16;  // byte offset in the A image
       const int row = o / RBA, pc = (o % RBA) / 16;
-      const int lc = pc ^ w2_swz<BF, RBA>(row);
+      const int lc = pc ^ swz_a(row);
       const int pix = p0 + row;
       const int c = a0 + lc * EPC;
       unsigned off = OOB;
@@ -235,7 +210,7 @@ __global__ __launch_bounds__(512) void wgrad2_kernel(const Grouped<Wgrad2Args, N
         const int n = dv_phpw.div(pix), rem = pix - n * PHPW;
         const int py = dv_pw.div(rem), px = rem - py * PW;
         int qy = py * qsh + ldy[j], qx = px * qsw + ldx[j];
-        if (pad_mode) { qy = w2_refl(qy, QH); qx = w2_refl(qx, QW); }
+        if (pad_mode) { qy = tpg_refl(qy, QH); qx = tpg_refl(qx, QW); }
         const bool ok = pix < pend && c < (FLAT ? p.cbp : Cb) && (unsigned)qy < (unsigned)QH && (unsigned)qx < (unsigned)QW;
         const unsigned o2 = (unsigned)((n * qsn + qy * qsh_ + qx * qsw_ + c) * ES);
         off = ok ? o2 : OOB;
@@ -259,7 +234,7 @@ __global__ __launch_bounds__(512) void wgrad2_kernel(const Grouped<Wgrad2Args, N
 #pragma unroll
     for (int n = 0; n < NREP; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4r{one_pair<DT>(), one_pair<DT>(), one_pair<DT>(), one_pair<DT>()});
+  const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4{one_pair<DT>(), one_pair<DT>(), one_pair<DT>(), one_pair<DT>()});
   // per-lane LDS byte offsets of the 16-bit fragment reads (see rd in compute)
   int abase[BF ? MREP : 1], bbase[BF ? NREP : 1];
   if constexpr (BF) {
@@ -267,12 +242,12 @@ __global__ __launch_bounds__(512) void wgrad2_kernel(const Grouped<Wgrad2Args, N
 #pragma unroll
     for (int m = 0; m < MREP; ++m) {
       const int col = wm * WTM + m * 16 + 4 * p4;
-      abase[m] = row * RBA + (((col >> 3) ^ w2_swz<BF, RBA>(row)) << 4) + (col & 7) * 2;
+      abase[m] = row * RBA + (((col >> 3) ^ swz_a(row)) << 4) + (col & 7) * 2;
     }
 #pragma unroll
     for (int n = 0; n < NREP; ++n) {
       const int col = wn * WTN + n * 16 + 4 * p4;
-      bbase[n] = row * RBB + (((col >> 3) ^ w2_swz<BF, RBB>(row)) << 4) + (col & 7) * 2;
+      bbase[n] = row * RBB + (((col >> 3) ^ swz_b(row)) << 4) + (col & 7) * 2;
     }
   }
 
@@ -295,9 +270,9 @@ __global__ __launch_bounds__(512) void wgrad2_kernel(const Grouped<Wgrad2Args, N
       // (lane bases: abase / bbase, computed once per block)
       auto rd = [&](int ks, int r) -> s16x4 {
         if constexpr ((TPG_W2_ABL & 8) != 0) return s16x4{(short)r, (short)ks, 1, 2};
-        if (r < 2 * MREP) return tr_read_o(A + abase[r >> 1], (32 * ks + 4 * (r & 1)) * RBA);
+        if (r < 2 * MREP) return tr_read(lds_addr(A + abase[r >> 1]), (32 * ks + 4 * (r & 1)) * RBA);
         const int rr = r - 2 * MREP;
-        return tr_read_o(B + bbase[rr >> 1], (32 * ks + 4 * (rr & 1)) * RBB);
+        return tr_read(lds_addr(B + bbase[rr >> 1]), (32 * ks + 4 * (rr & 1)) * RBB);
       };
       s16x4 h[2][R];
       // (first-use order, counted waits below: the MFMAs start on their own operands)
@@ -357,12 +332,12 @@ __global__ __launch_bounds__(512) void wgrad2_kernel(const Grouped<Wgrad2Args, N
 #pragma unroll
         for (int m = 0; m < MREP; ++m) {
           const int col = wm * WTM + m * 16 + l16;
-          av[m] = *reinterpret_cast<const float*>(A + row * RBA + (((col >> 2) ^ w2_swz<BF, RBA>(row)) << 4) + (col & 3) * 4);
+          av[m] = *reinterpret_cast<const float*>(A + row * RBA + (((col >> 2) ^ swz_a(row)) << 4) + (col & 3) * 4);
         }
 #pragma unroll
         for (int n = 0; n < NREP; ++n) {
           const int col = wn * WTN + n * 16 + l16;
-          bv[n] = *reinterpret_cast<const float*>(B + row * RBB + (((col >> 2) ^ w2_swz<BF, RBB>(row)) << 4) + (col & 3) * 4);
+          bv[n] = *reinterpret_cast<const float*>(B + row * RBB + (((col >> 2) ^ swz_b(row)) << 4) + (col & 3) * 4);
         }
 #pragma unroll
         for (int m = 0; m < MREP; ++m)

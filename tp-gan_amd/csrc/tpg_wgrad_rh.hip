@@ -15,7 +15,7 @@
 // ds_read_b64_tr_b16 fragment reads for v_mfma_f32_16x16x32_bf16, fp32 atomics over the
 // pixel splits.  Blocks of one pixel split are adjacent in the XCD-aware order, so the
 // tiles that read the same dY / X rows run together on one XCD's L2.
-#include "tpg_internal.h"
+#include "tpg_device.h"
 #include <type_traits>
 #include <utility>
 
@@ -26,41 +26,6 @@
 #endif
 
 namespace tpg {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4r;
-
-__device__ __forceinline__ s16x4 rh_tr_read(const char* p) {
-  s16x4 v;
-  const unsigned a = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(a));
-  return v;
-}
-// with a constant part of the address in the instruction's offset field (off: a constant once
-// the caller's loops are unrolled)
-__device__ __forceinline__ s16x4 rh_tr_read_o(const char* base, int off) {
-  s16x4 v;
-  const unsigned a = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)base;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(a), "i"(off));
-  return v;
-}
-
-
-// chunk swizzles of the LDS rows (256- and 128-byte rows as in tpg_wgrad2.hip; 64-byte rows:
-// the g = 0 / 1 row octets of a transposed read use disjoint chunk pairs)
-template <int RB>
-__device__ __forceinline__ int rh_swz(int row) {
-  if constexpr (RB == 256) return ((row & 3) | (((row >> 3) & 1) << 2)) << 1;
-  else if constexpr (RB == 128) return (((row >> 1) & 1) | (((row >> 3) & 1) << 1)) << 1;
-  else return ((row >> 3) & 1) << 1;
-}
-
-__device__ __forceinline__ int rh_refl(int i, int n) {
-  i = i < 0 ? -i : i;
-  return i >= n ? 2 * n - 2 - i : i;
-}
 
 // The tiles held to 128 VGPRs (two 512-thread blocks per CU)
 template <int NR, int NT, int BM, int BC>
@@ -82,6 +47,11 @@ void wgrad_rh_kernel(const WgradRHArgs p) {
   constexpr int WTM = BM / WM, WTN = BN / WN;
   constexpr int MREP = WTM / 16, NREP = WTN / 16;
   constexpr int RBA = BM * 2, RBB = BC * 2;  // LDS row bytes
+  // row size whose chunk swizzle the dY rows take (tr_swz, tpg_device.h; the X rows: RBB).  The
+  // 256-channel tile's 512-byte rows have always taken the 64-byte rows' mask -- the former
+  // three-way branch fell through to it -- which leaves the four rows R .. R + 3 of a transposed
+  // read on one chunk pair; kept bit for bit (the 256-byte mask is the candidate, to be timed)
+  constexpr int SWA = RBA == 512 ? 64 : RBA;
   constexpr int BYTES_A = KP * RBA;
   constexpr int GA = BYTES_A / 8192;         // 1 KiB DMA pieces per wave for dY
   constexpr int HROWS = NR == 1 ? 72 : 200;  // >= (TH + NR - 1) * (TW + NT - 1) halo pixels
@@ -138,7 +108,7 @@ void wgrad_rh_kernel(const WgradRHArgs p) {
 #pragma unroll
   for (int j = 0; j < GA; ++j) {
     const int row = (wave * GA + j) * RPP + lane / (RBA / 16), pc = lane % (RBA / 16);
-    const int c = a0 + ((pc ^ rh_swz<RBA>(row)) << 3);
+    const int c = a0 + ((pc ^ tr_swz<SWA>(row)) << 3);
     const bool live = c < p.Ca && row < TH * TW;
     aoff[j] = live ? (unsigned)(((row / TW) * p.p_sh + (row % TW) * p.p_sw + c) * 2) : OOB;
     ary[j] = live ? row / TW : (1 << 28);
@@ -149,7 +119,7 @@ void wgrad_rh_kernel(const WgradRHArgs p) {
 #pragma unroll
   for (int j = 0; j < GB; ++j) {
     const int row = (j * 8 + wave) * RPB + lane / (RBB / 16), pc = lane % (RBB / 16);
-    const int c = b0 + ((pc ^ rh_swz<RBB>(row)) << 3);
+    const int c = b0 + ((pc ^ tr_swz<RBB>(row)) << 3);
     bhy[j] = row / HW + r0 - p.pt;             // + py  = X row of this halo pixel
     bhx[j] = row % HW + s0 - p.pl;             // + px0 = X column
     bch[j] = (c < p.Cb && row < nhalo && j * 8 + wave < PB) ? c : -1;
@@ -171,7 +141,7 @@ void wgrad_rh_kernel(const WgradRHArgs p) {
     for (int j = 0; j < GB; ++j) {
       int qy = py_ + bhy[j], qx = px_ + bhx[j];
       bool ok = bch[j] >= 0;
-      if (p.pad_mode) { qy = rh_refl(qy, p.QH); qx = rh_refl(qx, p.QW); }
+      if (p.pad_mode) { qy = tpg_refl(qy, p.QH); qx = tpg_refl(qx, p.QW); }
       else ok = ok && (unsigned)qy < (unsigned)p.QH && (unsigned)qx < (unsigned)p.QW;
       const unsigned off = ok ? (unsigned)((n_ * p.q_sn + qy * p.q_sh + qx * p.q_sw + bch[j]) * 2) : OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rQ, (__attribute__((address_space(3))) void*)(st + BYTES_A + (j * 8 + wave) * 1024),
@@ -209,7 +179,7 @@ void wgrad_rh_kernel(const WgradRHArgs p) {
 #pragma unroll
     for (int j = 0; j < NREP; ++j) acc[m][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4r{one_pair<DT>(), one_pair<DT>(), one_pair<DT>(), one_pair<DT>()});
+  const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4{one_pair<DT>(), one_pair<DT>(), one_pair<DT>(), one_pair<DT>()});
 
   // Fragment reads (transposed, 4 channels x 4 pixels per lane and read): fragment r < 2*MREP
   // is dY (A), the rest X halo rows shifted by the column's tap.  Next substep's reads are
@@ -224,7 +194,7 @@ void wgrad_rh_kernel(const WgradRHArgs p) {
 #pragma unroll
     for (int m = 0; m < MREP; ++m) {
       const int col = wm * WTM + m * 16 + 4 * p4, row = 8 * g + q;
-      abase[m] = row * RBA + (((col >> 3) ^ rh_swz<RBA>(row)) << 4) + (col & 7) * 2;
+      abase[m] = row * RBA + (((col >> 3) ^ tr_swz<SWA>(row)) << 4) + (col & 7) * 2;
     }
 #pragma unroll
     for (int j = 0; j < NREP; ++j)
@@ -233,7 +203,7 @@ void wgrad_rh_kernel(const WgradRHArgs p) {
         const int col = wn * WTN + j * 16 + 4 * p4;
         const int tap = col / BC, cb = col % BC;
         const int row = 8 * g + 4 * h + q + tap;  // (row mode: halo row = pixel + tap)
-        bbase[j][h] = BYTES_A + row * RBB + (((cb >> 3) ^ rh_swz<RBB>(row)) << 4) + (cb & 7) * 2;
+        bbase[j][h] = BYTES_A + row * RBB + (((cb >> 3) ^ tr_swz<RBB>(row)) << 4) + (cb & 7) * 2;
       }
     // opaque to the optimiser: kept as one register each (rematerialised from their parts they
     // cost two VALU per read and k-tile)
@@ -265,23 +235,23 @@ void wgrad_rh_kernel(const WgradRHArgs p) {
       if (rr < 2 * MREP) {
         const int col = wm * WTM + (rr >> 1) * 16 + 4 * p4;
         const int row = ks * 32 + 8 * g + 4 * (rr & 1) + q;
-        return A + row * RBA + (((col >> 3) ^ rh_swz<RBA>(row)) << 4) + (col & 7) * 2;
+        return A + row * RBA + (((col >> 3) ^ tr_swz<SWA>(row)) << 4) + (col & 7) * 2;
       }
       const int r2 = rr - 2 * MREP;
       const int col = wn * WTN + (r2 >> 1) * 16 + 4 * p4;  // (tap, b) column
       const int tap = col / BC, cb = col % BC;
       const int row = kbase[ks][r2 & 1] + (tap / NT) * HW + tap % NT;
-      return B + row * RBB + (((cb >> 3) ^ rh_swz<RBB>(row)) << 4) + (cb & 7) * 2;
+      return B + row * RBB + (((cb >> 3) ^ tr_swz<RBB>(row)) << 4) + (cb & 7) * 2;
     };
     // IMM: lane base + constant offset (asm: a builtin LDS read makes hipcc put vmcnt(0) in
     // front of it for the in-flight LDS-DMA, measured +18 % on the 256 x 32 tile)
     auto rd = [&](int ks, int rr) -> s16x4 {
       if constexpr (IMM) {
-        if (rr < 2 * MREP) return rh_tr_read_o(A + abase[rr >> 1], (32 * ks + 4 * (rr & 1)) * RBA);
+        if (rr < 2 * MREP) return tr_read(lds_addr(A + abase[rr >> 1]), (32 * ks + 4 * (rr & 1)) * RBA);
         const int r2 = rr - 2 * MREP;
-        return rh_tr_read_o(A + bbase[r2 >> 1][r2 & 1], 32 * ks * RBB);
+        return tr_read(lds_addr(A + bbase[r2 >> 1][r2 & 1]), 32 * ks * RBB);
       } else {
-        return rh_tr_read(addr(ks, rr));
+        return tr_read(lds_addr(addr(ks, rr)));
       }
     };
     s16x4 h[2][R];
@@ -458,12 +428,7 @@ void wgrad_rh_kernel(const WgradRHArgs p) {
   }
 }
 
-// (helpers of the dense tile below)
-__device__ __forceinline__ s16x4 rd_tr_read_a(unsigned a, int off) {
-  s16x4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(a), "i"(off));
-  return v;
-}
+// (helper of the dense tile below)
 template <int... I, class F>
 __device__ __forceinline__ void rd_static_for(std::integer_sequence<int, I...>, F&& f) {
   (f(std::integral_constant<int, I>{}), ...);
@@ -507,7 +472,7 @@ constexpr RdSched rd_sched(int t_) {
 // shifted by its tap: 20 transposed reads per 25 MFMAs (0.8, against 1.9 on the 64 x 32 tile).
 //
 // LDS rows: the 160 live bytes of a pixel are kept in a 256-byte row with the 256-byte chunk
-// swizzle above; the DMA fetches only the 10 live 16-byte chunks of a row (lanes of the other
+// swizzle (tr_swz); the DMA fetches only the 10 live 16-byte chunks of a row (lanes of the other
 // 6 give an out-of-range offset, which moves nothing from memory and stores zeros).  Stage =
 // 64 dY rows + 72 halo rows = 34 KB, ring 102 KB, one block per CU.  Bank argument: a
 // transposed read takes, per 32-lane half, two 16-lane groups of 4 rows x 32 bytes (chunks
@@ -562,7 +527,7 @@ void wgrad_rd_kernel(const WgradRHArgs p) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int row = (wave * 2 + j) * 4 + (lane >> 4), pc = lane & 15;
-    const int c = (pc ^ rh_swz<RB>(row)) << 3;
+    const int c = (pc ^ tr_swz<RB>(row)) << 3;
     aoff[j] = c < p.Ca ? (unsigned)((row * p.p_sw + c) * 2) : OOB;
   }
   //   X piece j * 8 + wave (< PB): halo pixels (j * 8 + wave) * 4 .. + 3
@@ -570,7 +535,7 @@ void wgrad_rd_kernel(const WgradRHArgs p) {
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     const int row = (j * 8 + wave) * 4 + (lane >> 4), pc = lane & 15;
-    const int c = (pc ^ rh_swz<RB>(row)) << 3;
+    const int c = (pc ^ tr_swz<RB>(row)) << 3;
     bhx[j] = row - p.pl;                       // + px0 = X column
     bch[j] = (c < p.Cb && row < KP + NT - 1) ? c : -1;
   }
@@ -587,13 +552,13 @@ void wgrad_rd_kernel(const WgradRHArgs p) {
     }
     int qy = py_ + r0 - p.pt;
     const bool yok = p.pad_mode || (unsigned)qy < (unsigned)p.QH;
-    if (p.pad_mode) qy = rh_refl(qy, p.QH);
+    if (p.pad_mode) qy = tpg_refl(qy, p.QH);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       if (j == 2 && !third) break;
       int qx = px_ + bhx[j];
       bool ok = bch[j] >= 0 && yok;
-      if (p.pad_mode) qx = rh_refl(qx, p.QW);
+      if (p.pad_mode) qx = tpg_refl(qx, p.QW);
       else ok = ok && (unsigned)qx < (unsigned)p.QW;
       const unsigned off = ok ? (unsigned)((n_ * p.q_sn + qy * p.q_sh + qx * p.q_sw + bch[j]) * 2) : OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rQ, (__attribute__((address_space(3))) void*)(st + BYTES_A + (j * 8 + wave) * 1024),
@@ -614,7 +579,7 @@ void wgrad_rd_kernel(const WgradRHArgs p) {
 #pragma unroll
     for (int j = 0; j < NREP; ++j) acc[m][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4r{one_pair<DT>(), one_pair<DT>(), one_pair<DT>(), one_pair<DT>()});
+  const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4{one_pair<DT>(), one_pair<DT>(), one_pair<DT>(), one_pair<DT>()});
 
   // per-lane LDS byte offsets of the fragment reads (as in row mode above: the substep's + 32
   // rows and, for dY, the K half's + 4 rows leave the swizzle alone and go into the offset
@@ -627,7 +592,7 @@ void wgrad_rd_kernel(const WgradRHArgs p) {
 #pragma unroll
   for (int m = 0; m < MREP; ++m) {
     const int col = m * 16 + 4 * p4, row = 8 * g + q;
-    abase[m] = lds0 + row * RB + (((col >> 3) ^ rh_swz<RB>(row)) << 4) + (col & 7) * 2;
+    abase[m] = lds0 + row * RB + (((col >> 3) ^ tr_swz<RB>(row)) << 4) + (col & 7) * 2;
   }
 #pragma unroll
   for (int j = 0; j < NREP; ++j)
@@ -635,7 +600,7 @@ void wgrad_rd_kernel(const WgradRHArgs p) {
     for (int h = 0; h < 2; ++h) {
       const int col = j * 16 + 4 * p4;
       const int row = 8 * g + 4 * h + q + tap;  // halo row = pixel + tap
-      bbase[j][h] = lds0 + BYTES_A + row * RB + (((col >> 3) ^ rh_swz<RB>(row)) << 4) + (col & 7) * 2;
+      bbase[j][h] = lds0 + BYTES_A + row * RB + (((col >> 3) ^ tr_swz<RB>(row)) << 4) + (col & 7) * 2;
     }
   auto pin_bases = [&]() {
 #pragma unroll
@@ -658,12 +623,12 @@ void wgrad_rd_kernel(const WgradRHArgs p) {
     s16x4 fa[2][2], fb[2][NREP][2];
     auto rd_a = [&](auto grc) {  // dY fragment of global row gr = ks * MREP + m
       constexpr int gr = decltype(grc)::value, ks = gr / MREP, m = gr % MREP;
-      fa[gr & 1][0] = rd_tr_read_a(abase[m], (32 * ks) * RB);
-      fa[gr & 1][1] = rd_tr_read_a(abase[m], (32 * ks + 4) * RB);
+      fa[gr & 1][0] = tr_read(abase[m], (32 * ks) * RB);
+      fa[gr & 1][1] = tr_read(abase[m], (32 * ks + 4) * RB);
     };
     auto rd_b = [&](auto ksc, auto rrc) {  // read rr of substep ks: half rr & 1 of X fragment rr >> 1
       constexpr int ks = decltype(ksc)::value, rr = decltype(rrc)::value;
-      fb[ks & 1][rr >> 1][rr & 1] = rd_tr_read_a(bbase[rr >> 1][rr & 1], 32 * ks * RB);
+      fb[ks & 1][rr >> 1][rr & 1] = tr_read(bbase[rr >> 1][rr & 1], 32 * ks * RB);
     };
     rd_a(std::integral_constant<int, 0>{});
     rd_static_for(std::make_integer_sequence<int, 2 * NREP>{},
@@ -698,7 +663,7 @@ void wgrad_rd_kernel(const WgradRHArgs p) {
 #pragma unroll
     for (int ks = 0; ks < NS; ++ks)
 #pragma unroll
-      for (int rr = 0; rr < 2 * MREP; ++rr) h[ks][rr] = rd_tr_read_a(abase[rr >> 1], (32 * ks + 4 * (rr & 1)) * RB);
+      for (int rr = 0; rr < 2 * MREP; ++rr) h[ks][rr] = tr_read(abase[rr >> 1], (32 * ks + 4 * (rr & 1)) * RB);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
