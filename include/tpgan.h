@@ -120,7 +120,11 @@ typedef struct tpg_conv_desc {
                                      80 x (7 taps x 80): one block per kernel row of a 7-wide
                                      kernel with at most 80 channels on each side, a tap per
                                      wave (16-bit, output width a multiple of 64; no dead-block
-                                     skip); -30 when not covered */
+                                     skip); 14 = kernel-row halo kernel, dense five-tap tile: one
+                                     block per kernel row of a 5-wide kernel and per (a, b) tile of
+                                     at most 112 x 112 channels, the 5 x (b / 16) column blocks
+                                     dealt to the 8 waves (16-bit, output width a multiple of 64;
+                                     no dead-block skip); -30 when not covered */
   int32_t flags;                  /* TPG_FLAG_*: WPACKED = w.data is the image tpg_conv2d_pack_jobs /
                                      tpg_pack_run produced for this descriptor and op */
   int32_t data_ksplit;            /* 0 = automatic; >= 1 forces the k-step split of the forward and

@@ -31,6 +31,7 @@ SHAPES = {
     "conv6": (32, 64, 128, 128, 32, 3, 1, 1, False, 0, ACT_LEAKY, False),
     "enhance_64": (32, 208, 64, 64, 208, 3, 1, 1, False, 0, ACT_LEAKY, True),
     "add_64": (32, 80, 64, 64, 80, 5, 1, 2, False, 0, ACT_LEAKY, True),
+    "res5_64": (32, 64, 64, 64, 64, 5, 1, 2, False, 0, ACT_LEAKY, True),
     "enhance_32": (32, 416, 32, 32, 416, 3, 1, 1, False, 0, ACT_LEAKY, True),
     "enhance_16": (32, 768, 16, 16, 768, 3, 1, 1, False, 0, ACT_LEAKY, True),
     "up_128": (32, 208, 64, 64, 64, 3, 2, 1, True, 1, ACT_RELU, False),
@@ -124,7 +125,7 @@ def timed(fn, iters, graph):
     return e0.elapsed_time(e1) / iters
 
 
-SWEEP = {"algos": tuple(range(1, 14)), "ks": (1, 2, 4, 8, 16, 32, 64)}  # (--wg-sweep candidates)
+SWEEP = {"algos": tuple(range(1, 15)), "ks": (1, 2, 4, 8, 16, 32, 64)}  # (--wg-sweep candidates)
 
 
 def run(name, s, iters, passes, sweep=False, wg_algo=0, graph=False, dsplits=(), dalgo=0):

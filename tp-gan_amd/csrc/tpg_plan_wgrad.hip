@@ -19,6 +19,9 @@ static bool plan_wgrad_rh(const PlanCtx& cx, const tpg_conv_desc* d, const tpg_t
   // (<= 80) channels of both sides
   const bool dense = d->algo == 13;
   if (dense && (d->kw != 7 || d->out_c > 80 || d->in_c > 80)) return false;
+  // algo 14: the dense five-tap tile, one block per kernel row of a 5-wide kernel and (a, b) tile
+  const bool dense5 = d->algo == 14;
+  if (dense5 && d->kw != 5) return false;
   // image mode k-tile: th = floor(64 / tw) rows of tw = min(PW, 64); the fragment reads reach
   // halo row (63 / tw + kh - 1) * (tw + kw - 1) + tw + kw - 2, inside the 200-row LDS image
   const int tw = std::min(PW, 64);
@@ -48,9 +51,16 @@ static bool plan_wgrad_rh(const PlanCtx& cx, const tpg_conv_desc* d, const tpg_t
   a.tw = img ? tw : 64;
   // tile: fewest padded MACs, the 128 x 64 tile (best operand reuse) on ties
   int bm = 128, bc = 64;
-  if (d->algo >= 6 && d->algo <= 13) {
+  if (d->algo >= 6 && d->algo <= 14) {
     a.cfg = d->algo - 6;
     wgrad_rh_tile(a.cfg, &bm, &bc);
+    if (dense5) {
+      // channel tiles padded by at most one MFMA block: ceil(C / 112) tiles of ceil(C / tiles)
+      // channels, rounded up to 16 (206 -> 2 x 112, 80 -> 80, 64 -> 64)
+      bm = (int)rup(cdiv(a.Ca, cdiv(a.Ca, bm)), 16);
+      bc = (int)rup(cdiv(a.Cb, cdiv(a.Cb, bc)), 16);
+      a.tm = bm; a.tn = bc;
+    }
   } else {
     int64_t best = -1;
     for (int c = img ? 4 : 0; c < (img ? 6 : 4); ++c) {
@@ -72,7 +82,7 @@ static bool plan_wgrad_rh(const PlanCtx& cx, const tpg_conv_desc* d, const tpg_t
   } else {
     // pixel splits: whole rounds of resident blocks (one per CU, two for the <= 128-VGPR
     // tiles) against the fp32 atomics every extra split adds (~1.3 TB/s of added bytes)
-    const int resident = (img || a.cfg == 6 || a.cfg == 7 ? 256 : (a.cfg == 3 || (a.cfg != 0 && a.nt <= 4)) ? 512 : 256) / cx.share;
+    const int resident = (img || a.cfg >= 6 ? 256 : (a.cfg == 3 || (a.cfg != 0 && a.nt <= 4)) ? 512 : 256) / cx.share;
     const int taps = a.nr * a.nt;
     const double flops = 2.0 * a.tiles * bm * taps * bc * 64.0 * a.nkt;
     double best = -1;
@@ -92,14 +102,14 @@ static bool plan_wgrad_rh(const PlanCtx& cx, const tpg_conv_desc* d, const tpg_t
   // bias MFMAs spread over up to 16 / ksplit tiles: same-address atomics serialise (~50 ns
   // each), so blocks x splits adding into one dbias row must stay few
   a.bshare = cx.det ? 1 : std::max(1, std::min(a.ntb * a.nrg * cdiv(a.kw, a.nt), 16 / a.ksplit));
-  a.skip = dense ? 0 : 1;  // (the dense tile has no dead-block skip)
+  a.skip = dense || dense5 ? 0 : 1;  // (the dense tiles have no dead-block skip)
   p->kernel = img ? TPG_WGRAD_IMAGE_HALO : TPG_WGRAD_ROW_HALO;
   p->cfg = a.cfg; p->bm = bm; p->bn = bc; p->tiles = a.tiles;
   return true;
 }
 
 // Validates the call and plans it: the row/image-halo kernel where it applies (desc.algo 0 or
-// 6..13), else the flat DMA kernel on 16-byte aligned rows, else the generic kernel.
+// 6..14), else the flat DMA kernel on 16-byte aligned rows, else the generic kernel.
 int32_t plan_bwd_filter(const tpg_conv_desc* d, const tpg_tensor& x, const tpg_tensor& g, const tpg_tensor& dw,
                                WgradPlan* p) {
   int32_t rc = check_desc(d);
@@ -148,7 +158,7 @@ int32_t plan_bwd_filter(const tpg_conv_desc* d, const tpg_tensor& x, const tpg_t
   p->sums_bias = !d->transposed;
   // kernel-row halo kernel (stride-1 Conv2d, bf16, 64-pixel row segments): algo 6, and the
   // default for untuned calls when it applies
-  const bool rh_algo = d->algo >= 6 && d->algo <= 13;
+  const bool rh_algo = d->algo >= 6 && d->algo <= 14;
   if ((d->algo == 0 || rh_algo) && !comp && !d->transposed && plan_wgrad_rh(cx, d, x, g, dw, p)) return 0;
   if (rh_algo) return fail(-30, "wgrad: row-halo kernel does not apply to this shape");
   // pipelined DMA kernel when both operands are 16-byte aligned channels-last rows

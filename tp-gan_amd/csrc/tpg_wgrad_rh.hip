@@ -439,10 +439,13 @@ __device__ __forceinline__ void rd_static_for(std::integer_sequence<int, I...>, 
 // a substep that is not the last: the next substep's B reads i * 2 NR / M .. (i + 1) * 2 NR / M.
 // LDS reads return in order, so MFMA t waits for lgkmcnt(issued - 1 - need): the reads issued
 // before it, less those up to the last one it needs.
-struct RdSched {
-  static constexpr int NS = 2, MR = 5, NR = 5, M = MR * NR, T = NS * M;
+template <int MR_, int NR_>
+struct RdSchedT {
+  static constexpr int NS = 2, MR = MR_, NR = NR_, M = MR * NR, T = NS * M;
+  static_assert(MR >= 2, "at most one B read per MFMA");
   int issued, need;
 };
+template <class RdSched>
 constexpr RdSched rd_sched(int t_) {
   int ia[RdSched::NS * RdSched::MR] = {}, ib[RdSched::NS][RdSched::NR] = {};  // last read of each fragment
   int n = 2;
@@ -460,6 +463,7 @@ constexpr RdSched rd_sched(int t_) {
   const int a = ia[ks * RdSched::MR + i / RdSched::NR], b = ib[ks][i % RdSched::NR];
   return RdSched{n, a > b ? a : b};
 }
+using RdSched = RdSchedT<5, 5>;  // (wgrad_rd_kernel's 5 x 5 blocks per tap wave)
 
 // ---- Dense tap-per-wave tile (desc.algo 13, tile id 7): 7-wide kernels with at most 80 channels
 // on each side.  The tiles above cut 75 dY channels into two 64-row tiles and 75 X channels
@@ -637,7 +641,7 @@ void wgrad_rd_kernel(const WgradRHArgs p) {
     rd_static_for(std::make_integer_sequence<int, RdSched::T>{}, [&](auto tc) {
       constexpr int t = decltype(tc)::value, ks = t / RdSched::M, i = t % RdSched::M, m = i / NREP, j = i % NREP;
       constexpr int gr = ks * MREP + m;
-      constexpr RdSched sc = rd_sched(t);
+      constexpr RdSched sc = rd_sched<RdSched>(t);
       constexpr int w = sc.issued - 1 - sc.need < 15 ? sc.issued - 1 - sc.need : 15;
       static_assert(w >= 0, "a fragment is read before its MFMA");
       asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(w) : "memory");
@@ -786,9 +790,328 @@ void wgrad_rd_kernel(const WgradRHArgs p) {
   }
 }
 
+// ---- Dense five-tap tile (desc.algo 14, tile id 8): 5-wide kernels of any channel count.  The
+// row-halo tiles above give a wave 32 x 80 of a 128 x (5 x 32) tile: 1.87 transposed reads per
+// MFMA, and 80 channels pad to 128 x 96.  Here a block owns one kernel row r, all 5 taps, an a-tile
+// of p.tm dY channels and a b-tile of p.tn X channels (the planner cuts C channels into
+// ceil(C / 112) tiles of ceil(C / tiles) rounded up to 16: 206 -> 112 + 94, 80 -> 80, 64 -> 64), so
+// 5 x NB column blocks (tap, b-block), NB = p.tn / 16.  They are dealt to the 8 waves in fixed
+// order: slot j of wave w is column block w + 8 j = tap * NB + b-block, and every wave holds all
+// MR block rows of its NRW = ceil(5 NB / 8) slots.  Every wave reads the same MR dY row fragments
+// and its own X fragments at (tap shift, b-block) offsets, which are per-wave uniform and live in
+// the per-lane base addresses: (2 MR + 2 NRW) reads per MR x NRW MFMAs, 24 / 35 on the 112 x 112
+// tile.  Block rows past p.tm and slots past 5 NB multiply zeros (no branch around an MFMA):
+// the rows were stored as zeros by the DMA, the slots read a zero constant behind the ring.
+// 8 NRW > 5 NB for every NB <= 7, so the last slot of wave 7 is always spare: it reads a constant
+// of ones during the k-tiles whose bias sum the block owns (zeros otherwise) and its accumulators
+// are the dY row sums.
+//
+// LDS rows, DMA, ring, pipeline, read schedule, block order and epilogue are wgrad_rd_kernel's
+// (a 256-byte row holds up to 128 channels of a tile; only the live chunks are fetched).
+template <int DT, int MR, int NRW>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1)))
+void wgrad_rd5_kernel(const WgradRHArgs p) {
+  constexpr int KP = 64, NT = 5, RB = 256;
+  constexpr int BYTES_A = KP * RB;
+  constexpr int HROWS = 72;                  // >= 64 + NT - 1 halo pixels, whole 1 KiB pieces
+  constexpr int PB = HROWS * RB / 1024;      // X pieces: 18 = 2 per wave + one more on waves 0, 1
+  constexpr int STAGE = BYTES_A + HROWS * RB;
+  constexpr int SUB = 32 * RB;               // LDS bytes from a substep's rows to the next one's
+  // constants behind the ring: 512 bytes of ones, then 512 of zeros, and again SUB further on
+  // (a spare slot's lanes read 8 bytes each at lane * 8, plus the substep's offset field)
+  constexpr int CONSTS = 3 * STAGE;
+  using Sched = RdSchedT<MR, NRW>;
+  static_assert(PB > 16 && PB <= 24 && KP * RB == 16 * 1024, "dma pieces");
+  static_assert(MR <= 7 && NRW <= 5, "tiles of at most 112 x 112 channels");
+
+  extern __shared__ __attribute__((aligned(16))) char lds[];  // [3][STAGE], constants
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  // (XCD-aware block order as above; logical = split * tiles + (a-tile, b-tile, kernel row))
+  const int nblk = gridDim.x, full = nblk & ~7, bid = blockIdx.x;
+  const int L = bid < full ? (bid & 7) * (full >> 3) + (bid >> 3) : bid;
+  const int tile = L % p.tiles, split = L / p.tiles;
+  const int ta = tile % p.nta, tb = (tile / p.nta) % p.ntb, r0 = tile / (p.nta * p.ntb);
+  const int a0 = ta * p.tm, b0 = tb * p.tn;
+  const int alim = min(p.Ca, a0 + p.tm), blim = min(p.Cb, b0 + p.tn);
+  const int NB = p.tn >> 4, ncb = NT * NB;   // column blocks of the tile
+  const int kt0 = split * p.kt_per_split;
+  const int nkt = min(p.nkt, kt0 + p.kt_per_split) - kt0;
+  if (nkt <= 0) return;
+  // bias gradient: k-tile kt of the split is summed by the a-tile's block (b-tile, kernel row)
+  // of share index kt % bshare
+  const int sid = tb + p.ntb * r0;
+  const bool bias_wave = p.dbias != nullptr && sid < p.bshare && wave == 7;
+
+  const int segs = p.PW / KP;
+  int n = kt0 / (p.PH * segs);
+  int rem = kt0 - n * p.PH * segs;
+  int py = rem / segs;
+  int px0 = (rem % segs) * KP;
+
+  const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.P), 0, p.p_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rQ = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.Q), 0, p.q_bytes, 0x00020000);
+  constexpr unsigned OOB = 0x80000000u;
+
+  // per-lane constants of the DMA pieces (4 rows x 16 chunks each; chunk pc of a row holds the
+  // tile's channels 8 * (pc ^ swizzle) ..)
+  //   dY piece 2 * wave + j: pixels (2 * wave + j) * 4 .. + 3 of the k-tile
+  unsigned aoff[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int row = (wave * 2 + j) * 4 + (lane >> 4), pc = lane & 15;
+    const int c = a0 + ((pc ^ tr_swz<RB>(row)) << 3);
+    aoff[j] = c < alim ? (unsigned)((row * p.p_sw + c) * 2) : OOB;
+  }
+  //   X piece j * 8 + wave (< PB): halo pixels (j * 8 + wave) * 4 .. + 3
+  int bhx[3], bch[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int row = (j * 8 + wave) * 4 + (lane >> 4), pc = lane & 15;
+    const int c = b0 + ((pc ^ tr_swz<RB>(row)) << 3);
+    bhx[j] = row - p.pl;                       // + px0 = X column
+    bch[j] = (c < blim && row < KP + NT - 1) ? c : -1;
+  }
+  const bool third = wave < PB - 16;           // this wave issues a third X piece
+
+  auto issue = [&](int slot, int n_, int py_, int px_) {
+    char* st = lds + slot * STAGE;
+    const int sbase = (n_ * p.p_sn + py_ * p.p_sh + px_ * p.p_sw) * 2;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const unsigned vo = aoff[j];
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rP, (__attribute__((address_space(3))) void*)(st + (wave * 2 + j) * 1024),
+                                               16, vo, sbase, 0, 0);
+    }
+    int qy = py_ + r0 - p.pt;
+    const bool yok = p.pad_mode || (unsigned)qy < (unsigned)p.QH;
+    if (p.pad_mode) qy = tpg_refl(qy, p.QH);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      if (j == 2 && !third) break;
+      int qx = px_ + bhx[j];
+      bool ok = bch[j] >= 0 && yok;
+      if (p.pad_mode) qx = tpg_refl(qx, p.QW);
+      else ok = ok && (unsigned)qx < (unsigned)p.QW;
+      const unsigned off = ok ? (unsigned)((n_ * p.q_sn + qy * p.q_sh + qx * p.q_sw + bch[j]) * 2) : OOB;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rQ, (__attribute__((address_space(3))) void*)(st + BYTES_A + (j * 8 + wave) * 1024),
+                                               16, off, 0, 0, 0);
+    }
+  };
+
+  const int g = lane >> 4, l16 = lane & 15;
+  const int q = l16 >> 2, p4 = l16 & 3;
+  f32x4 acc[MR][NRW];
+#pragma unroll
+  for (int m = 0; m < MR; ++m)
+#pragma unroll
+    for (int j = 0; j < NRW; ++j) acc[m][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // the constants (made visible by the first k-tile's barrier)
+  if (tid < 256) {
+    const unsigned v = tid < 128 ? one_pair<DT>() : 0u;
+    unsigned* cs = reinterpret_cast<unsigned*>(lds + CONSTS);
+    cs[tid] = v;
+    cs[tid + SUB / 4] = v;
+  }
+
+  // per-lane LDS byte addresses of the fragment reads in ring slot 0 (as in wgrad_rd_kernel: the
+  // substep's + 32 rows and, for dY, the K half's + 4 rows go into the offset field; the X bases
+  // carry the slot's tap shift and b-block).  Spare slots stay on the constants.
+  unsigned abase[MR], bbase[NRW][2];
+  const unsigned lds0 = lds_addr(lds);
+  const unsigned zeros = lds0 + CONSTS + 512 + lane * 8;
+  // the last slot of a wave when it is spare: ones while the block's bias wave owns k-tile kt
+  auto spare_base = [&](int kt) -> unsigned {
+    return bias_wave && (kt0 + kt) % p.bshare == sid ? zeros - 512 : zeros;
+  };
+#pragma unroll
+  for (int m = 0; m < MR; ++m) {
+    const int col = m * 16 + 4 * p4, row = 8 * g + q;
+    abase[m] = lds0 + row * RB + (((col >> 3) ^ tr_swz<RB>(row)) << 4) + (col & 7) * 2;
+  }
+  bool slot_live[NRW];
+#pragma unroll
+  for (int j = 0; j < NRW; ++j) {
+    const int cb = wave + 8 * j;
+    slot_live[j] = cb < ncb;
+    const int tap = slot_live[j] ? cb / NB : 0, bb = slot_live[j] ? cb % NB : 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int col = bb * 16 + 4 * p4;
+      const int row = 8 * g + 4 * h + q + tap;  // halo row = pixel + tap
+      const unsigned live = lds0 + BYTES_A + row * RB + (((col >> 3) ^ tr_swz<RB>(row)) << 4) + (col & 7) * 2;
+      bbase[j][h] = slot_live[j] ? live : (j == NRW - 1 ? spare_base(0) : zeros);
+    }
+  }
+  auto pin_bases = [&]() {
+#pragma unroll
+    for (int m = 0; m < MR; ++m) asm volatile("" : "+v"(abase[m]));
+#pragma unroll
+    for (int j = 0; j < NRW; ++j) {
+      asm volatile("" : "+v"(bbase[j][0]));
+      asm volatile("" : "+v"(bbase[j][1]));
+    }
+  };
+  pin_bases();
+
+  // a wave's k-tile: NS x MR x NRW MFMAs, m-major, every one behind a counted wait for its own two
+  // fragments (rd_sched); rolling A and double-set B fragment registers as in wgrad_rd_kernel
+  constexpr int NS = Sched::NS;
+  static_assert(NS * 32 == KP, "substeps");
+  auto compute = [&]() {
+    s16x4 fa[2][2], fb[2][NRW][2];
+    auto rd_a = [&](auto grc) {  // dY fragment of global row gr = ks * MR + m
+      constexpr int gr = decltype(grc)::value, ks = gr / MR, m = gr % MR;
+      fa[gr & 1][0] = tr_read(abase[m], ks * SUB);
+      fa[gr & 1][1] = tr_read(abase[m], ks * SUB + 4 * RB);
+    };
+    auto rd_b = [&](auto ksc, auto rrc) {  // read rr of substep ks: half rr & 1 of X fragment rr >> 1
+      constexpr int ks = decltype(ksc)::value, rr = decltype(rrc)::value;
+      fb[ks & 1][rr >> 1][rr & 1] = tr_read(bbase[rr >> 1][rr & 1], ks * SUB);
+    };
+    rd_a(std::integral_constant<int, 0>{});
+    rd_static_for(std::make_integer_sequence<int, 2 * NRW>{},
+                  [&](auto rrc) { rd_b(std::integral_constant<int, 0>{}, rrc); });
+    __builtin_amdgcn_sched_barrier(0);
+    rd_static_for(std::make_integer_sequence<int, Sched::T>{}, [&](auto tc) {
+      constexpr int t = decltype(tc)::value, ks = t / Sched::M, i = t % Sched::M, m = i / NRW, j = i % NRW;
+      constexpr int gr = ks * MR + m;
+      constexpr Sched sc = rd_sched<Sched>(t);
+      constexpr int w = sc.issued - 1 - sc.need < 15 ? sc.issued - 1 - sc.need : 15;
+      static_assert(w >= 0, "a fragment is read before its MFMA");
+      asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(w) : "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      const bf16x8 av = __builtin_bit_cast(bf16x8, __builtin_shufflevector(fa[gr & 1][0], fa[gr & 1][1],
+                                                                           0, 1, 2, 3, 4, 5, 6, 7));
+      const bf16x8 bv = __builtin_bit_cast(bf16x8, __builtin_shufflevector(fb[ks & 1][j][0], fb[ks & 1][j][1],
+                                                                           0, 1, 2, 3, 4, 5, 6, 7));
+      acc[m][j] = mfma16x16x32<DT>(av, bv, acc[m][j]);
+      // (the order rd_sched counts in: the next A row, then the next substep's B reads)
+      if constexpr (j == 0 && gr + 1 < NS * MR) rd_a(std::integral_constant<int, gr + 1>{});
+      if constexpr (ks + 1 < NS) {
+        constexpr int lo = i * 2 * NRW / Sched::M, hi = (i + 1) * 2 * NRW / Sched::M;
+        if constexpr (hi > lo) rd_b(std::integral_constant<int, ks + 1>{}, std::integral_constant<int, lo>{});
+        static_assert(hi - lo <= 1, "at most one B read per MFMA");
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    });
+  };
+
+  // pipeline: k-tile i in ring slot i % 3, issued two k-tiles ahead (clamped: static vmcnt)
+  int in_ = n, iy = py, ix = px0, issued = 0;  // position of the next k-tile to issue
+  auto issue_next = [&](int slot) {
+    issue(slot, in_, iy, ix);
+    if (++issued < nkt) {
+      ix += KP;
+      if (ix == p.PW) { ix = 0; if (++iy == p.PH) { iy = 0; ++in_; } }
+    }
+  };
+  // (the newest k-tile's DMAs stay in flight: 5 on waves 0 and 1, 4 on the others)
+  auto wait_barrier = [&]() {
+    if (third) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  };
+  issue_next(0);
+  issue_next(1);
+  wait_barrier();  // retires k-tile 0 (and the constants)
+  int slot = 0;
+  for (int kt = 0; kt < nkt; ++kt) {
+    issue_next(slot == 0 ? 2 : slot - 1);
+    compute();
+    wait_barrier();  // retires k-tile kt+1, kt+2 stays in flight
+    // the fragment bases follow the ring; the spare slots stay, the last one by the bias share
+    const int step = slot == 2 ? -2 * STAGE : STAGE;
+#pragma unroll
+    for (int m = 0; m < MR; ++m) abase[m] += step;
+#pragma unroll
+    for (int j = 0; j < NRW; ++j) {
+      const int sj = slot_live[j] ? step : 0;
+      bbase[j][0] += sj;
+      bbase[j][1] += sj;
+    }
+    if (!slot_live[NRW - 1]) bbase[NRW - 1][0] = bbase[NRW - 1][1] = spare_base(kt + 1);
+    pin_bases();
+    slot = slot == 2 ? 0 : slot + 1;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+
+  // ---- epilogue as above, in chunks of 16 dW rows (one MFMA block row of every wave); tile
+  // column = column block * 16 + l16 = tap * p.tn + b
+  const int BN = ncb * 16, LDC = BN + 4;
+  static_assert(16 * (NT * 112 + 4) * 4 <= 3 * STAGE, "a block row of the C tile fits in the LDS ring");
+  float* Cs = reinterpret_cast<float*>(lds);
+  const int amax = alim - a0;
+  auto col_off = [&](int col) -> int {  // dW element offset of tile column col at a = 0; -1: padding
+    const int s = col / p.tn, b = b0 + col % p.tn;
+    if (b >= p.Cb) return -1;
+    return b * p.w_sb + r0 * p.w_sr + s * p.w_ss;
+  };
+  constexpr int CG = 2 * NRW;  // 64-column groups: 5 NB <= 8 NRW
+  int coff[CG];
+#pragma unroll
+  for (int c = 0; c < CG; ++c) coff[c] = (c * 64 + lane < BN) ? col_off(c * 64 + lane) : -1;
+  const bool vec_base = p.w_sb == 1 && (p.w_sa & 3) == 0 && ((uintptr_t)p.dW & 15) == 0;
+  asm volatile("s_barrier" ::: "memory");  // (every wave's DMAs retired above: the ring is free)
+#pragma unroll
+  for (int m = 0; m < MR; ++m) {
+    if (m > 0) __syncthreads();  // the previous chunk has been read
+#pragma unroll
+    for (int j = 0; j < NRW; ++j)
+      if (slot_live[j]) {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) Cs[(4 * g + reg) * LDC + (wave + 8 * j) * 16 + l16] = acc[m][j][reg];
+      }
+    __syncthreads();
+    const int rows = min(16, amax - m * 16);  // (<= 0 past the a-tile: nothing to add)
+    if (p.ksplit == 1) {
+      const int CPR = BN / 4;
+      for (int idx = tid; idx < rows * CPR; idx += 512) {
+        const int row = idx / CPR, cc = 4 * (idx - row * CPR);
+        const float4 v = *reinterpret_cast<const float4*>(Cs + row * LDC + cc);
+        float* dst = p.dW + (a0 + m * 16 + row) * p.w_sa;
+        const int o0 = col_off(cc);
+        if (vec_base && o0 >= 0 && (o0 & 3) == 0 && col_off(cc + 3) == o0 + 3) {
+          float4* d4 = reinterpret_cast<float4*>(dst + o0);
+          float4 o = *d4;
+          o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w;
+          *d4 = o;
+        } else {
+          const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int oe = col_off(cc + e);
+            if (oe >= 0) dst[oe] += vv[e];
+          }
+        }
+      }
+    } else {
+      for (int row = wave; row < rows; row += 8) {
+        float* dst = p.dW + (a0 + m * 16 + row) * p.w_sa;
+#pragma unroll
+        for (int c = 0; c < CG; ++c)
+          if (coff[c] >= 0) atomicAdd(dst + coff[c], Cs[row * LDC + c * 64 + lane]);
+      }
+    }
+  }
+  if (bias_wave && l16 == 0) {  // every column of the spare slot holds the row sum
+#pragma unroll
+    for (int m = 0; m < MR; ++m)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int a = a0 + m * 16 + 4 * g + reg;
+        if (a >= alim) continue;
+        if (p.ksplit == 1 && p.bshare == 1) p.dbias[a] += acc[m][NRW - 1][reg];
+        else atomicAdd(p.dbias + a, acc[m][NRW - 1][reg]);
+      }
+  }
+}
+
 // tile configs {id, BM, BC}; id = desc.algo - 6 (ids 4, 5: image mode, 32-channel b tiles;
 // id 6: row mode, 256 dY channels per block, waves 64 x (NT x 32) / 2; id 7: the dense
-// 80 x (7 x 80) tile, wgrad_rd_kernel)
+// 80 x (7 x 80) tile, wgrad_rd_kernel; id 8: the dense five-tap tile, wgrad_rd5_kernel)
 #define TPG_WGRAD_RH_CFGS(X) \
   X(0, 128, 64)              \
   X(1, 128, 32)              \
@@ -803,7 +1126,32 @@ int wgrad_rh_tile(int cfg, int* bm, int* bc) {
   TPG_WGRAD_RH_CFGS(X)
 #undef X
   if (cfg == 7) { *bm = 80; *bc = 80; return 0; }
+  if (cfg == 8) { *bm = 112; *bc = 112; return 0; }  // (the largest; the planner fits them to the channels)
   return -1;
+}
+
+template <int MR, int NRW>
+static int launch_rd5_t(const WgradRHArgs& a, hipStream_t s) {
+  const size_t lds = 3 * (64 + 72) * 256 + 32 * 256 + 1024;  // ring, constants
+  auto k1 = wgrad_rd5_kernel<1, MR, NRW>;
+  auto k2 = wgrad_rd5_kernel<2, MR, NRW>;
+  static bool once = ((void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                      (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                      true);
+  (void)once;
+  hipLaunchKernelGGL(a.dtype == 2 ? k2 : k1, dim3(a.tiles * a.ksplit), dim3(512), lds, s, a);
+  return (int)hipGetLastError();
+}
+
+// the smallest instance (block rows, column slots per wave) that holds the tile: 112 x 112
+// (7, 5), 80 x 80 (5, 4), 64 x 112 (4, 5).  (A (4, 3) instance for 64 x 64 was correct and lost its
+// sweep to the 64 x 32 row-halo tile on the 64 -> 64 layer, so it is not built: such tiles
+// run on (4, 5).)
+static int launch_rd5(const WgradRHArgs& a, hipStream_t s) {
+  const int mr = a.tm / 16, nrw = (5 * (a.tn / 16) + 7) / 8;
+  if (mr <= 4) return launch_rd5_t<4, 5>(a, s);
+  if (mr <= 5 && nrw <= 4) return launch_rd5_t<5, 4>(a, s);
+  return launch_rd5_t<7, 5>(a, s);
 }
 
 static int launch_rd(const WgradRHArgs& a, hipStream_t s) {
@@ -857,6 +1205,10 @@ int launch_wgrad_rh(const WgradRHArgs& a, hipStream_t s) {
 #undef X
   if (a.cfg == 7 && a.nr == 1 && a.nt == 7 && a.kw == 7 && a.Ca <= 80 && a.Cb <= 80 && a.tw == 64 && a.tiles == a.kh)
     return launch_rd(a, s);
+  if (a.cfg == 8 && a.nr == 1 && a.nt == 5 && a.kw == 5 && a.tw == 64 && a.tm >= 16 && a.tm <= 112 && a.tm % 16 == 0 &&
+      a.tn >= 16 && a.tn <= 112 && a.tn % 16 == 0 && a.nta * a.tm >= a.Ca && a.ntb * a.tn >= a.Cb &&
+      a.tiles == a.nta * a.ntb * a.kh)
+    return launch_rd5(a, s);
   return -1;
 }
 

@@ -430,13 +430,15 @@ def _tuned_wgrad(lib, d, x, g, dwv):
     def launch():
         return lib.tpg_conv2d_bwd_filter(ctypes.byref(s), tt(x), tt(g), tt(scratch), None, 0, stream_ptr())
     torch.cuda.synchronize()
-    for algo in range(1, 14):
+    for algo in range(1, 15):
+        if algo == 14 and d.kw != 5:  # the dense five-tap tile: no trial call where it cannot apply
+            continue
         for ks in _WG_SPLITS:
             if ks > nkt or (ks > 16 and (d.flags & FLAG_CONCURRENT)):
                 break
             s.algo, s.ksplit = algo, ks
             rc = launch()
-            if rc == -30:  # algos 6..13 (row / image-halo kernel) do not cover this shape
+            if rc == -30:  # algos 6..14 (row / image-halo kernel) do not cover this shape
                 break
             check(rc)
             t = _time_launches(lambda: check(launch()))
