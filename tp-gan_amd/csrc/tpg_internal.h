@@ -233,7 +233,7 @@ struct WgradRHArgs {
   int cfg;                    // tile: 0 = 128 x 64, 1 = 128 x 32, 2 = 64 x 64, 3 = 64 x 32 (a x b);
                               // image mode: 4 = 128 x 32, 5 = 64 x 32; 6 = 256 x 32; 7 = the dense
                               // 80 x (7 taps x 80) tap-per-wave tile (wgrad_rd_kernel); 8 = the dense
-                              // five-tap tile tm x (5 taps x tn) (wgrad_rd5_kernel)
+                              // five-tap tile tm x (5 taps x tn) (wgrad_dense_kernel, NT = 5)
   int tm, tn;                 // cfg 8: channels of an a-tile / b-tile (multiples of 16, <= 112)
   int nta, ntb, tiles;        // tiles = nta * ntb * kh * groups
   int nkt, kt_per_split, ksplit;

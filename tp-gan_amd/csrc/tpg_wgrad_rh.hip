@@ -34,6 +34,22 @@ constexpr bool rh_fits128() {
                                  (BM == 64 && BC == 32)));
 }
 
+// XCD-aware block order: physical block b runs on XCD b % 8 and each XCD is handed a contiguous
+// range of logical blocks (this block's is returned)
+__device__ __forceinline__ int xcd_logical_block() {
+  const int nblk = gridDim.x, full = nblk & ~7, bid = blockIdx.x;
+  return bid < full ? (bid & 7) * (full >> 3) + (bid >> 3) : bid;
+}
+// buffer resource of a DMA operand: offsets at or past `bytes` read zero
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t dma_rsrc(const void* base, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
+}
+
+// dynamic LDS of wgrad_rh_kernel: three stages of 64 dY rows and the X halo in whole rounds of
+// eight 1 KiB pieces
+template <int NR, int BM, int BC>
+constexpr int rh_lds_bytes() { return 3 * (64 * BM * 2 + ((NR == 1 ? 72 : 200) * BC * 2 + 8191) / 8192 * 8192); }
+
 template <int DT, int NR, int NT, int BM, int BC>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(rh_fits128<NR, NT, BM, BC>() ? 4 : 1)))
 void wgrad_rh_kernel(const WgradRHArgs p) {
@@ -61,15 +77,13 @@ void wgrad_rh_kernel(const WgradRHArgs p) {
   constexpr int STAGE = BYTES_A + GB * 8 * 1024;
   static_assert(NR == 1 ? ((NT >= 3 && NT <= 5) || NT == 7) : (NR == NT && NT <= 3), "taps per block");
   static_assert(GA * 8192 == BYTES_A && GA >= 1 && GB <= 2, "dma pieces");
+  static_assert(3 * STAGE == rh_lds_bytes<NR, BM, BC>(), "the launcher's LDS size");
   static_assert(MREP * 16 * WM == BM && NREP * 16 * WN == BN, "waves");
 
   extern __shared__ __attribute__((aligned(16))) char lds[];  // [3][STAGE]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
 
-  // XCD-aware block order: physical block b runs on XCD b % 8 and each XCD is handed a
-  // contiguous range of logical blocks; logical = split * tiles + tile.
-  const int nblk = gridDim.x, full = nblk & ~7, bid = blockIdx.x;
-  const int L = bid < full ? (bid & 7) * (full >> 3) + (bid >> 3) : bid;
+  const int L = xcd_logical_block();  // = split * tiles + tile
   const int tile = L % p.tiles, split = L / p.tiles;
   int t = tile;
   const int ta = t % p.nta; t /= p.nta;
@@ -97,8 +111,7 @@ void wgrad_rh_kernel(const WgradRHArgs p) {
   int py = (rem / segs) * TH;
   int px0 = (rem % segs) * TW;
 
-  const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.P), 0, p.p_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rQ = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.Q), 0, p.q_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rP = dma_rsrc(p.P, p.p_bytes), rQ = dma_rsrc(p.Q, p.q_bytes);
   constexpr unsigned OOB = 0x80000000u;
 
   // per-lane constants of the DMA pieces
@@ -325,14 +338,8 @@ void wgrad_rh_kernel(const WgradRHArgs p) {
 #if (TPG_RH_ABL & 2) != 0
 #define RH_WAIT_BARRIER() asm volatile("s_waitcnt vmcnt(6)\n\ts_waitcnt lgkmcnt(0)" ::: "memory")
 #else
-#define RH_WAIT_BARRIER()                                                                          \
-  do {                                                                                             \
-    if constexpr (GA + GB == 2) asm volatile("s_waitcnt vmcnt(2)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
-    else if constexpr (GA + GB == 3) asm volatile("s_waitcnt vmcnt(3)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
-    else if constexpr (GA + GB == 4) asm volatile("s_waitcnt vmcnt(4)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
-    else if constexpr (GA + GB == 5) asm volatile("s_waitcnt vmcnt(5)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
-    else asm volatile("s_waitcnt vmcnt(6)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");    \
-  } while (0)
+#define RH_WAIT_BARRIER() \
+  asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(GA + GB) : "memory")
 #endif
   static_assert(GA + GB >= 2 && GA + GB <= 6, "vmcnt");
   issue_next(0);
@@ -428,7 +435,7 @@ void wgrad_rh_kernel(const WgradRHArgs p) {
   }
 }
 
-// (helper of the dense tile below)
+// (helper of the dense tiles below)
 template <int... I, class F>
 __device__ __forceinline__ void rd_static_for(std::integer_sequence<int, I...>, F&& f) {
   (f(std::integral_constant<int, I>{}), ...);
@@ -463,6 +470,7 @@ constexpr RdSched rd_sched(int t_) {
   const int a = ia[ks * RdSched::MR + i / RdSched::NR], b = ib[ks][i % RdSched::NR];
   return RdSched{n, a > b ? a : b};
 }
+
 using RdSched = RdSchedT<5, 5>;  // (wgrad_rd_kernel's 5 x 5 blocks per tap wave)
 
 // ---- Dense tap-per-wave tile (desc.algo 13, tile id 7): 7-wide kernels with at most 80 channels
@@ -489,6 +497,7 @@ using RdSched = RdSchedT<5, 5>;  // (wgrad_rd_kernel's 5 x 5 blocks per tap wave
 //
 // Pipeline, epilogue and block order are those of wgrad_rh_kernel.  18 X pieces over 8 waves:
 // waves 0 and 1 issue 5 DMA instructions per k-tile, the others 4, and each waits on its own count.
+constexpr int rd_lds_bytes() { return 3 * (64 + 72) * 256; }  // dynamic LDS: the ring
 template <int DT>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1)))
 void wgrad_rd_kernel(const WgradRHArgs p) {
@@ -499,14 +508,13 @@ void wgrad_rd_kernel(const WgradRHArgs p) {
   constexpr int PB = HROWS * RB / 1024;      // X pieces: 18 = 2 per wave + one more on waves 0, 1
   constexpr int STAGE = BYTES_A + HROWS * RB;
   static_assert(PB > 16 && PB <= 24 && KP * RB == 16 * 1024, "dma pieces");
+  static_assert(3 * STAGE == rd_lds_bytes(), "the launcher's LDS size");
 
   extern __shared__ __attribute__((aligned(16))) char lds[];  // [3][STAGE]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  // (XCD-aware block order as above; logical = split * tiles + kernel row)
-  const int nblk = gridDim.x, full = nblk & ~7, bid = blockIdx.x;
-  const int L = bid < full ? (bid & 7) * (full >> 3) + (bid >> 3) : bid;
+  const int L = xcd_logical_block();  // = split * tiles + kernel row
   const int r0 = L % p.tiles, split = L / p.tiles;
   const int kt0 = split * p.kt_per_split;
   const int nkt = min(p.nkt, kt0 + p.kt_per_split) - kt0;
@@ -521,8 +529,7 @@ void wgrad_rd_kernel(const WgradRHArgs p) {
   int py = rem / segs;
   int px0 = (rem % segs) * KP;
 
-  const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.P), 0, p.p_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rQ = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.Q), 0, p.q_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rP = dma_rsrc(p.P, p.p_bytes), rQ = dma_rsrc(p.Q, p.q_bytes);
   constexpr unsigned OOB = 0x80000000u;
 
   // per-lane constants of the DMA pieces (4 rows x 16 chunks each)
@@ -790,28 +797,33 @@ void wgrad_rd_kernel(const WgradRHArgs p) {
   }
 }
 
-// ---- Dense five-tap tile (desc.algo 14, tile id 8): 5-wide kernels of any channel count.  The
-// row-halo tiles above give a wave 32 x 80 of a 128 x (5 x 32) tile: 1.87 transposed reads per
-// MFMA, and 80 channels pad to 128 x 96.  Here a block owns one kernel row r, all 5 taps, an a-tile
+// ---- Dense tile of NT taps (NT = 5: desc.algo 14, tile id 8, 5-wide kernels of any channel count).
+// The row-halo tiles above give a wave 32 x 80 of a 128 x (5 x 32) tile: 1.87 transposed reads per
+// MFMA, and 80 channels pad to 128 x 96.  Here a block owns one kernel row r, all NT taps, an a-tile
 // of p.tm dY channels and a b-tile of p.tn X channels (the planner cuts C channels into
 // ceil(C / 112) tiles of ceil(C / tiles) rounded up to 16: 206 -> 112 + 94, 80 -> 80, 64 -> 64), so
-// 5 x NB column blocks (tap, b-block), NB = p.tn / 16.  They are dealt to the 8 waves in fixed
+// NT x NB column blocks (tap, b-block), NB = p.tn / 16.  They are dealt to the 8 waves in fixed
 // order: slot j of wave w is column block w + 8 j = tap * NB + b-block, and every wave holds all
-// MR block rows of its NRW = ceil(5 NB / 8) slots.  Every wave reads the same MR dY row fragments
+// MR block rows of its NRW = ceil(NT NB / 8) slots.  Every wave reads the same MR dY row fragments
 // and its own X fragments at (tap shift, b-block) offsets, which are per-wave uniform and live in
 // the per-lane base addresses: (2 MR + 2 NRW) reads per MR x NRW MFMAs, 24 / 35 on the 112 x 112
-// tile.  Block rows past p.tm and slots past 5 NB multiply zeros (no branch around an MFMA):
+// tile.  Block rows past p.tm and slots past NT NB multiply zeros (no branch around an MFMA):
 // the rows were stored as zeros by the DMA, the slots read a zero constant behind the ring.
-// 8 NRW > 5 NB for every NB <= 7, so the last slot of wave 7 is always spare: it reads a constant
-// of ones during the k-tiles whose bias sum the block owns (zeros otherwise) and its accumulators
-// are the dY row sums.
+// 8 NRW > NT NB for every tile the launcher gives an instance, so the last slot of wave 7 is always
+// spare: it reads a constant of ones during the k-tiles whose bias sum the block owns (zeros
+// otherwise) and its accumulators are the dY row sums.  (<NT = 7, MR = 5, NRW = 5> is algo 13 bit
+// for bit and lost the launch timing to wgrad_rd_kernel, profiles/r14/refactor_ab.txt: not built.)
 //
 // LDS rows, DMA, ring, pipeline, read schedule, block order and epilogue are wgrad_rd_kernel's
 // (a 256-byte row holds up to 128 channels of a tile; only the live chunks are fetched).
-template <int DT, int MR, int NRW>
+
+// dynamic LDS: the ring, then the constants (1 KiB of ones and zeros, and again SUB further on)
+constexpr int dense_lds_bytes() { return rd_lds_bytes() + 32 * 256 + 1024; }
+
+template <int DT, int NT, int MR, int NRW>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1)))
-void wgrad_rd5_kernel(const WgradRHArgs p) {
-  constexpr int KP = 64, NT = 5, RB = 256;
+void wgrad_dense_kernel(const WgradRHArgs p) {
+  constexpr int KP = 64, RB = 256;
   constexpr int BYTES_A = KP * RB;
   constexpr int HROWS = 72;                  // >= 64 + NT - 1 halo pixels, whole 1 KiB pieces
   constexpr int PB = HROWS * RB / 1024;      // X pieces: 18 = 2 per wave + one more on waves 0, 1
@@ -821,16 +833,15 @@ void wgrad_rd5_kernel(const WgradRHArgs p) {
   // (a spare slot's lanes read 8 bytes each at lane * 8, plus the substep's offset field)
   constexpr int CONSTS = 3 * STAGE;
   using Sched = RdSchedT<MR, NRW>;
-  static_assert(PB > 16 && PB <= 24 && KP * RB == 16 * 1024, "dma pieces");
+  static_assert(PB > 16 && PB <= 24 && KP * RB == 16 * 1024 && KP + NT - 1 <= HROWS, "dma pieces");
+  static_assert(CONSTS + SUB + 1024 == dense_lds_bytes(), "the launcher's LDS size");
   static_assert(MR <= 7 && NRW <= 5, "tiles of at most 112 x 112 channels");
 
   extern __shared__ __attribute__((aligned(16))) char lds[];  // [3][STAGE], constants
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  // (XCD-aware block order as above; logical = split * tiles + (a-tile, b-tile, kernel row))
-  const int nblk = gridDim.x, full = nblk & ~7, bid = blockIdx.x;
-  const int L = bid < full ? (bid & 7) * (full >> 3) + (bid >> 3) : bid;
+  const int L = xcd_logical_block();  // = split * tiles + (a-tile, b-tile, kernel row)
   const int tile = L % p.tiles, split = L / p.tiles;
   const int ta = tile % p.nta, tb = (tile / p.nta) % p.ntb, r0 = tile / (p.nta * p.ntb);
   const int a0 = ta * p.tm, b0 = tb * p.tn;
@@ -850,8 +861,7 @@ void wgrad_rd5_kernel(const WgradRHArgs p) {
   int py = rem / segs;
   int px0 = (rem % segs) * KP;
 
-  const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.P), 0, p.p_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rQ = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.Q), 0, p.q_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rP = dma_rsrc(p.P, p.p_bytes), rQ = dma_rsrc(p.Q, p.q_bytes);
   constexpr unsigned OOB = 0x80000000u;
 
   // per-lane constants of the DMA pieces (4 rows x 16 chunks each; chunk pc of a row holds the
@@ -1049,7 +1059,7 @@ void wgrad_rd5_kernel(const WgradRHArgs p) {
     if (b >= p.Cb) return -1;
     return b * p.w_sb + r0 * p.w_sr + s * p.w_ss;
   };
-  constexpr int CG = 2 * NRW;  // 64-column groups: 5 NB <= 8 NRW
+  constexpr int CG = 2 * NRW;  // 64-column groups: NT NB <= 8 NRW
   int coff[CG];
 #pragma unroll
   for (int c = 0; c < CG; ++c) coff[c] = (c * 64 + lane < BN) ? col_off(c * 64 + lane) : -1;
@@ -1111,7 +1121,8 @@ void wgrad_rd5_kernel(const WgradRHArgs p) {
 
 // tile configs {id, BM, BC}; id = desc.algo - 6 (ids 4, 5: image mode, 32-channel b tiles;
 // id 6: row mode, 256 dY channels per block, waves 64 x (NT x 32) / 2; id 7: the dense
-// 80 x (7 x 80) tile, wgrad_rd_kernel; id 8: the dense five-tap tile, wgrad_rd5_kernel)
+// 80 x (7 x 80) tile, wgrad_rd_kernel; id 8: the dense five-tap tile, wgrad_dense_kernel -- its
+// largest; the planner fits them to the channels)
 #define TPG_WGRAD_RH_CFGS(X) \
   X(0, 128, 64)              \
   X(1, 128, 32)              \
@@ -1119,68 +1130,59 @@ void wgrad_rd5_kernel(const WgradRHArgs p) {
   X(3, 64, 32)               \
   X(4, 128, 32)              \
   X(5, 64, 32)               \
-  X(6, 256, 32)
+  X(6, 256, 32)              \
+  X(7, 80, 80)               \
+  X(8, 112, 112)
 
 int wgrad_rh_tile(int cfg, int* bm, int* bc) {
 #define X(id, BM_, BC_) if (cfg == (id)) { *bm = BM_; *bc = BC_; return 0; }
   TPG_WGRAD_RH_CFGS(X)
 #undef X
-  if (cfg == 7) { *bm = 80; *bc = 80; return 0; }
-  if (cfg == 8) { *bm = 112; *bc = 112; return 0; }  // (the largest; the planner fits them to the channels)
   return -1;
 }
 
-template <int MR, int NRW>
-static int launch_rd5_t(const WgradRHArgs& a, hipStream_t s) {
-  const size_t lds = 3 * (64 + 72) * 256 + 32 * 256 + 1024;  // ring, constants
-  auto k1 = wgrad_rd5_kernel<1, MR, NRW>;
-  auto k2 = wgrad_rd5_kernel<2, MR, NRW>;
-  static bool once = ((void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                      (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+// sets the dynamic-LDS limit of a kernel's bf16 / fp16 pair once and launches one of the two:
+// tiles * ksplit blocks of 512 threads
+template <auto K1, auto K2, int LDS>
+static int launch_pair(const WgradRHArgs& a, hipStream_t s) {
+  static bool once = ((void)hipFuncSetAttribute((const void*)K1, hipFuncAttributeMaxDynamicSharedMemorySize, LDS),
+                      (void)hipFuncSetAttribute((const void*)K2, hipFuncAttributeMaxDynamicSharedMemorySize, LDS),
                       true);
   (void)once;
-  hipLaunchKernelGGL(a.dtype == 2 ? k2 : k1, dim3(a.tiles * a.ksplit), dim3(512), lds, s, a);
+  hipLaunchKernelGGL(a.dtype == 2 ? K2 : K1, dim3(a.tiles * a.ksplit), dim3(512), LDS, s, a);
   return (int)hipGetLastError();
 }
 
-// the smallest instance (block rows, column slots per wave) that holds the tile: 112 x 112
-// (7, 5), 80 x 80 (5, 4), 64 x 112 (4, 5).  (A (4, 3) instance for 64 x 64 was correct and lost its
-// sweep to the 64 x 32 row-halo tile on the 64 -> 64 layer, so it is not built: such tiles
+template <int NT, int MR, int NRW>
+static int launch_dense_t(const WgradRHArgs& a, hipStream_t s) {
+  return launch_pair<wgrad_dense_kernel<1, NT, MR, NRW>, wgrad_dense_kernel<2, NT, MR, NRW>, dense_lds_bytes()>(a, s);
+}
+
+// five-tap tiles: the smallest instance (block rows, column slots per wave) that holds the tile:
+// 112 x 112 (7, 5), 80 x 80 (5, 4), 64 x 112 (4, 5).  (A (4, 3) instance for 64 x 64 was correct and
+// lost its sweep to the 64 x 32 row-halo tile on the 64 -> 64 layer, so it is not built: such tiles
 // run on (4, 5).)
-static int launch_rd5(const WgradRHArgs& a, hipStream_t s) {
-  const int mr = a.tm / 16, nrw = (5 * (a.tn / 16) + 7) / 8;
-  if (mr <= 4) return launch_rd5_t<4, 5>(a, s);
-  if (mr <= 5 && nrw <= 4) return launch_rd5_t<5, 4>(a, s);
-  return launch_rd5_t<7, 5>(a, s);
+static int launch_dense5(const WgradRHArgs& a, hipStream_t s) {
+  constexpr int NT = 5;
+  // (nb <= 7, and nb <= 6 where nrw <= 4: wave 7's last slot, column block 8 NRW - 1, stays spare)
+  static_assert(8 * 5 > NT * 7 && 8 * 4 > NT * 6, "the bias slot");
+  const int mr = a.tm / 16, nb = a.tn / 16, nrw = (NT * nb + 7) / 8;
+  if (mr <= 4) return launch_dense_t<NT, 4, 5>(a, s);
+  if (mr <= 5 && nrw <= 4) return launch_dense_t<NT, 5, 4>(a, s);
+  return launch_dense_t<NT, 7, 5>(a, s);
 }
 
 static int launch_rd(const WgradRHArgs& a, hipStream_t s) {
-  const size_t lds = 3 * (64 + 72) * 256;
-  auto k1 = wgrad_rd_kernel<1>;
-  auto k2 = wgrad_rd_kernel<2>;
-  static bool once = ((void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                      (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                      true);
-  (void)once;
-  hipLaunchKernelGGL(a.dtype == 2 ? k2 : k1, dim3(a.tiles * a.ksplit), dim3(512), lds, s, a);
-  return (int)hipGetLastError();
+  return launch_pair<wgrad_rd_kernel<1>, wgrad_rd_kernel<2>, rd_lds_bytes()>(a, s);
 }
 
 template <int NR, int NT, int BM, int BC>
 static int launch_rh_t(const WgradRHArgs& a, hipStream_t s) {
-  constexpr int GB = (((NR == 1 ? 72 : 200) * BC * 2 + 1023) / 1024 + 7) / 8;
-  const size_t lds = 3 * (64 * BM * 2 + GB * 8 * 1024);
-  auto k1 = wgrad_rh_kernel<1, NR, NT, BM, BC>;
-  auto k2 = wgrad_rh_kernel<2, NR, NT, BM, BC>;
-  static bool once = ((void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                      (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                      true);
-  (void)once;
-  hipLaunchKernelGGL(a.dtype == 2 ? k2 : k1, dim3(a.tiles * a.ksplit), dim3(512), lds, s, a);
-  return (int)hipGetLastError();
+  return launch_pair<wgrad_rh_kernel<1, NR, NT, BM, BC>, wgrad_rh_kernel<2, NR, NT, BM, BC>, rh_lds_bytes<NR, BM, BC>()>(a, s);
 }
 
-// row-mode configs instantiate the 1 x {3,4,5} tap groups, image-mode ones the 2x2 / 3x3
+// row-mode configs instantiate the 1 x {3,4,5} tap groups, image-mode ones the 2x2 / 3x3 (the
+// dense ids 7 and 8 have their own launchers)
 template <int ID, int BM, int BC>
 static int launch_rh_cfg(const WgradRHArgs& a, hipStream_t s) {
   if constexpr (ID < 4 || ID == 6) {
@@ -1191,7 +1193,7 @@ static int launch_rh_cfg(const WgradRHArgs& a, hipStream_t s) {
     // column; only the tiles whose 7 x BC columns keep the fragments within the VGPR budget
     if constexpr (ID >= 1 && ID <= 3)
       if (a.nr == 1 && a.nt == 7) return launch_rh_t<1, 7, BM, BC>(a, s);
-  } else {
+  } else if constexpr (ID < 6) {
     if (a.nr == 2 && a.nt == 2) return launch_rh_t<2, 2, BM, BC>(a, s);
     if (a.nr == 3 && a.nt == 3) return launch_rh_t<3, 3, BM, BC>(a, s);
   }
@@ -1199,16 +1201,16 @@ static int launch_rh_cfg(const WgradRHArgs& a, hipStream_t s) {
 }
 
 int launch_wgrad_rh(const WgradRHArgs& a, hipStream_t s) {
-#define X(id, BM_, BC_) \
-  if (a.cfg == (id)) return launch_rh_cfg<id, BM_, BC_>(a, s);
-  TPG_WGRAD_RH_CFGS(X)
-#undef X
   if (a.cfg == 7 && a.nr == 1 && a.nt == 7 && a.kw == 7 && a.Ca <= 80 && a.Cb <= 80 && a.tw == 64 && a.tiles == a.kh)
     return launch_rd(a, s);
   if (a.cfg == 8 && a.nr == 1 && a.nt == 5 && a.kw == 5 && a.tw == 64 && a.tm >= 16 && a.tm <= 112 && a.tm % 16 == 0 &&
       a.tn >= 16 && a.tn <= 112 && a.tn % 16 == 0 && a.nta * a.tm >= a.Ca && a.ntb * a.tn >= a.Cb &&
       a.tiles == a.nta * a.ntb * a.kh)
-    return launch_rd5(a, s);
+    return launch_dense5(a, s);
+#define X(id, BM_, BC_) \
+  if (a.cfg == (id)) return launch_rh_cfg<id, BM_, BC_>(a, s);
+  TPG_WGRAD_RH_CFGS(X)
+#undef X
   return -1;
 }
 
